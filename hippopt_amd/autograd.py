@@ -1,0 +1,126 @@
+"""torch autograd for the kinodynamic NLP of a batch of trajectories on one device.
+
+    nlp = KinodynamicNLP(settings, model, batch=B)        # one engine handle (hipnlp_create) on cuda:`device`
+    nlp.set_params(p)                                      # [B, np]
+    f, g = nlp(x)                                          # x: [B, n] float64 cuda tensor -> f [B], g [B, m]
+    loss = a * f.sum() + (w * g).sum()
+    loss.backward()                                        # x.grad = a grad f + J^T w, ONE launch (hipnlp_eval_lagrangian_grad_device)
+
+The forward pass is hipnlp_eval_device with grad f and jac g left out; the backward pass is the Lagrangian gradient
+sigma grad f + J^T lambda with sigma = df, lambda = dg (zeros for an output whose gradient is None): the Jacobian never reaches memory.
+Both run on torch.cuda.current_stream().  Not twice differentiable (once_differentiable); no derivative with respect to the parameters.
+torch is imported when first needed."""
+import numbers
+
+import numpy as np
+
+from .hipnlp import HipNlp
+
+_FUNCTION = None
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def _function():
+    """the torch.autograd.Function (built at first use: torch is imported lazily)"""
+    global _FUNCTION
+    if _FUNCTION is None:
+        torch = _torch()
+        from torch.autograd.function import once_differentiable
+
+        class NLPFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x, nlp):
+                f = torch.empty(nlp.batch, dtype=torch.float64, device=x.device)
+                g = torch.empty(nlp.batch, nlp.m, dtype=torch.float64, device=x.device)
+                nlp._forward(x, f, g)
+                ctx.save_for_backward(x)
+                ctx.nlp = nlp
+                return f, g
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, df, dg):
+                (x,) = ctx.saved_tensors
+                nlp = ctx.nlp
+                sigma = df.to(torch.float64).contiguous() if df is not None else torch.zeros(nlp.batch, dtype=torch.float64, device=x.device)
+                lam = dg.to(torch.float64).contiguous() if dg is not None else torch.zeros(nlp.batch, nlp.m, dtype=torch.float64, device=x.device)
+                return nlp._launch(x, sigma, lam), None
+
+        _FUNCTION = NLPFunction
+    return _FUNCTION
+
+
+class KinodynamicNLP:
+    """(f, g) = nlp(x) on a [batch, n] float64 tensor of cuda:`device`, differentiable in x.  detect_simple_bounds: the reduced NLP
+    (HIPNLP_FLAG_DETECT_SIMPLE_BOUNDS): g and lambda have the m rows of that problem."""
+
+    def __init__(self, settings, model, batch, device=0, detect_simple_bounds=False):
+        self.engine = HipNlp(settings, model, batch=batch, device=device, detect_simple_bounds=detect_simple_bounds)
+        self.batch, self.n, self.m, self.np = self.engine.batch, self.engine.n, self.engine.m, self.engine.np
+        self.device_index = int(device)
+
+    @property
+    def device(self):
+        return _torch().device("cuda", self.device_index)
+
+    def set_params(self, p):
+        """p [batch, np] (numpy array or tensor): the parameters of every trajectory"""
+        if hasattr(p, "detach"):
+            p = p.detach().cpu().numpy()
+        self.engine.set_params(np.asarray(p, dtype=np.float64))
+
+    def __call__(self, x):
+        """(f [batch], g [batch, m]); differentiable in x"""
+        self._check("x", x, (self.batch, self.n))
+        return _function().apply(x, self)
+
+    def lagrangian_gradient(self, x, sigma, lam):
+        """sigma grad f(x) + J(x)^T lam per trajectory ([batch, n]): sigma a number or a [batch] tensor, lam [batch, m]"""
+        torch = _torch()
+        self._check("x", x, (self.batch, self.n))
+        if isinstance(sigma, numbers.Real):
+            sigma = torch.full((self.batch,), float(sigma), dtype=torch.float64, device=self.device)
+        self._check("sigma", sigma, (self.batch,))
+        self._check("lam", lam, (self.batch, self.m))
+        return self._launch(x, sigma, lam)
+
+    # ---- internals ------------------------------------------------------------------------------------------------------------------
+    def _on_current_stream(self, launch):
+        """launch(stream handle), ordered on torch.cuda.current_stream().  A NULL stream means the handle's OWN stream to the library
+        (include/hipnlp.h), so on torch's default stream the launch goes to a private stream that waits for the current one, and the
+        current one waits for it (tensors are allocated on the current stream: nothing of it runs before the launch has ended)."""
+        torch = _torch()
+        cur = torch.cuda.current_stream(self.device)
+        if cur.cuda_stream:
+            launch(cur.cuda_stream)
+            return
+        if getattr(self, "_side", None) is None:
+            self._side = torch.cuda.Stream(device=self.device)
+        self._side.wait_stream(cur)
+        launch(self._side.cuda_stream)
+        cur.wait_stream(self._side)
+
+    def _forward(self, x, f, g):
+        self._on_current_stream(lambda s: self.engine.eval_device(x.data_ptr(), f.data_ptr(), 0, g.data_ptr(), 0, stream=s))
+
+    def _launch(self, x, sigma, lam):
+        out = _torch().empty_like(x, memory_format=_torch().contiguous_format)
+        self._on_current_stream(lambda s: self.engine.eval_lagrangian_grad_device(x.data_ptr(), sigma.data_ptr(), lam.data_ptr(), out.data_ptr(), stream=s))
+        return out
+
+    def _check(self, name, t, shape):
+        torch = _torch()
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: a torch.Tensor, not %s" % (name, type(t).__name__))
+        if t.dtype != torch.float64:
+            raise TypeError("%s: dtype float64, not %s" % (name, t.dtype))
+        if t.device != self.device:
+            raise ValueError("%s: on %s, not %s" % (name, self.device, t.device))
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("%s: shape %s, not %s" % (name, tuple(shape), tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("%s: a contiguous tensor" % name)

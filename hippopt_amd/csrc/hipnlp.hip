@@ -1086,6 +1086,160 @@ void hipnlp_knot_hess_kernel(HArgs a) {
 #endif
 }
 
+// =====================================================================================================================
+// Lagrangian gradient  xbar = sigma grad f(x) + J(x)^T lambda  (hipnlp_eval_lagrangian_grad_device).  Every entry of jac g whose column
+// belongs to knot k is emitted by knot k's program, so the knot's 189 columns of J^T lambda are sums over entries its workgroup holds in
+// LDS: one workgroup of four waves per (trajectory, knot) runs the knot program of the four-wave callback kernel — the same emitter, the
+// same compact scratch, every entry of jac g staged, constants included — and then sums column by column (knot_lgrad.h) in the (column,
+// row) order of Layout::lg_ent, whatever the handle's jac order.  No atomics, no second workgroup per column, no cost reduction: 189
+// doubles leave per knot (the last one also writes the six horizon-global columns) instead of the 1 849 of f, grad f, g and jac g.
+// The multipliers of the rows a block touches (its own rows and the trapezoid-defect rows of knot k + 1) are loaded at entry and held in
+// registers across the program; the entry words of the block are fetched behind the last barrier but one.  Both go into scratch that is
+// dead once the program has ended.
+// =====================================================================================================================
+constexpr int LG_SPAN_GLOB = 192;   // threads 192 .. 192 + NXG - 1 of the last knot sum the horizon-global columns
+static_assert(NXK <= LG_SPAN_GLOB && LG_SPAN_GLOB + NXG <= 256, "lgrad column threads");
+struct alignas(16) LgradTables {
+    int32_t word[3][LG_ENT_CAP + 16];   // entry e of a variant-v block: native slot | multiplier position << LG_SLOT_BITS (-1 behind);
+                                        // [LG_ENT_CAP ..): the horizon-global entries (last knot)
+    int32_t beg[3][256], end[3][256];   // entries [beg, end) of the column thread t sums (empty: nothing)
+    int32_t row_a[3][LG_LAM_CAP], row_b[3][LG_LAM_CAP];   // multiplier q of a knot k of variant v: lambda[row_a + row_b k] (G_NONE behind)
+};
+struct LArgs {
+    const DeviceTables* tb;
+    const LgradTables* lt;
+    const double* x;        // [batch][n]
+    const double* pk;
+    const GParams* gp;
+    const double* sigma;    // [batch]
+    const double* lambda;   // [batch][m]
+    double* out;            // [batch][n]
+    int32_t* flag;          // [batch] the handle's non-finite flag (== seq after a launch that produced one)
+    int32_t N, n, m, seq;
+};
+template <class S> __device__ __forceinline__ int32_t* lgrad_word_stage(S& s) { return reinterpret_cast<int32_t*>(&s.Uj[0][0]); }
+template <int TERRAIN> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4)))
+void hipnlp_knot_lgrad_kernel(LArgs a) {
+    using Em = DevEm<TERRAIN, 4, false>;   // (the four-wave callback kernel's emitter: the same program, the same bits of grad f and jac g)
+    using Scratch = typename Em::Scratch;
+    static_assert(Scratch::compact && !Scratch::trimmed, "the compact scratch of the four-wave callback kernel");
+    constexpr int WG = 256;
+    __shared__ Scratch s;
+    __shared__ SharedTablesT<true> tabs;
+    static_assert(sizeof(Scratch) + sizeof(SharedTablesT<true>) <= 40 * 1024, "four workgroups per CU: 40 KB of LDS each");
+    // the entry words go where Uj, Rw, ow, aw, wv, vo and comp were (contiguous doubles, dead once the program has ended)
+    static_assert(offsetof(Scratch, comp) + sizeof(Scratch::comp) - offsetof(Scratch, Uj) >= (LG_ENT_CAP + 16) * sizeof(int32_t), "lgrad entry staging");
+    constexpr int LQ = LG_LAM_CAP / WG, LE = LG_ENT_CAP / WG;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int b = blockIdx.y;
+    const int k = int((blockIdx.x & 7u) * (gridDim.x >> 3) + min(blockIdx.x & 7u, gridDim.x & 7u) + (blockIdx.x >> 3));   // (XCD-aware, as in hipnlp_knot_kernel)
+    const int N = a.N;
+    const int first = k == 0, last = k == N - 1;
+    const int v = first ? VAR_FIRST : (last ? VAR_LAST : VAR_INTERIOR);
+    const double* x = a.x + size_t(b) * a.n;
+    const DeviceTables& tb = *a.tb;
+    const LgradTables& lt = *a.lt;
+    double lv[LQ];
+    int ra[LQ], rb[LQ];
+    double sig = 0.0;
+    {
+        // staged as in hipnlp_knot_kernel: records and tables straight from global memory into LDS, 1 KB chunks dealt over the waves
+        constexpr int WAVES = WG / 64;
+        constexpr int XB = NXK * 8 / 16 * 16, XREM = NXK - XB / 8;
+        const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+        int rot = 0;
+        auto stage = [&](const void* src, void* dst, int bytes) __attribute__((always_inline)) {
+            for (int r0 = 0; r0 < bytes; r0 += WG * 16) {
+                const int wv = (wave_u + WAVES - rot % WAVES) & (WAVES - 1);
+                const int off = r0 + wv * 1024 + lane * 16;
+                if (off < bytes)
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(static_cast<const char*>(src) + off),
+                                                     (__attribute__((address_space(3))) void*)(static_cast<char*>(dst) + r0 + wv * 1024), 16, 0, 0);
+                rot += ((bytes - r0 < WG * 16 ? bytes - r0 : WG * 16) + 1023) / 1024;
+            }
+        };
+#pragma unroll
+        for (int it = 0; it < LQ; ++it) { ra[it] = lt.row_a[v][tid + it * WG]; rb[it] = lt.row_b[v][tid + it * WG]; }
+        sig = a.sigma[b];
+        stage(x + size_t(NXK) * k, s.x, XB);
+        if (!first) stage(x + size_t(NXK) * (k - 1), s.xm, XB); else rot += (XB + 1023) / 1024;
+        stage(a.pk + (size_t(b) * N + k) * PK_STRIDE, s.pk, PK_STRIDE * 8);
+        stage(x + size_t(NXK) * N, s.xg, NXG * 8);
+        stage(static_cast<const GParamsLite*>(a.gp + b), &tabs.gp, int(sizeof(GParamsLite)));
+        stage(&tb.head.ks, &tabs.ks, int(sizeof(KSettings)));
+        stage(static_cast<const KinLite*>(&tb.head.kt), &tabs.kt, int(sizeof(KinLite)));
+        double xrem = 0.0, xov = 0.0;
+        if (XREM && tid < 2 && !(first && tid == 1)) xrem = x[size_t(NXK) * (k - tid) + XB / 8];
+        if (first || last) { if (tid < NPER) xov = x[size_t(NXK) * (first ? N - 1 : 0) + periodicity_row_var(tid)]; }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the staging loads of THIS wave have landed in LDS
+        if (first || last) { if (tid < NPER) s.xo[tid] = xov; }
+        if (XREM && tid < 2) (tid ? s.xm : s.x)[XB / 8] = xrem;
+        if (first) { for (int i = tid; i < XB / 8; i += WG) s.xm[i] = 0.0; }
+        if (tid >= 64 && tid < 64 + Scratch::xpad - NXK) { s.x[NXK + tid - 64] = 0.0; s.xm[NXK + tid - 64] = 0.0; }
+        if (tid >= 128 && tid < 128 + 8 - NXG) s.xg[NXG + tid - 128] = 0.0;
+        // the multipliers: issued now, in flight across the (LDS-only) barriers of the program, staged once it has ended
+        const double* lam = a.lambda + size_t(b) * a.m;
+#pragma unroll
+        for (int it = 0; it < LQ; ++it) lv[it] = ra[it] != G_NONE ? lam[ra[it] + rb[it] * k] : 0.0;
+    }
+    lds_barrier();
+    // the entry words of the block and the column this thread sums: fetched behind the last barrier but one (their registers are free
+    // while the kinematic phases run)
+    int32_t w[LE], wg = -1, e0 = 0, e1 = 0;
+    auto fetch_tables = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int it = 0; it < LE; ++it) w[it] = lt.word[v][tid + it * WG];
+        wg = lt.word[v][LG_ENT_CAP + (tid & 15)];
+        e0 = lt.beg[v][tid]; e1 = lt.end[v][tid];
+    };
+    KnotInfo ki{k, N, first, last};
+    Em em{s.g, s.jac};
+    Ctx<Em> cx(s, tabs.kin(), tabs.settings(), tabs.gp, ki, em, &tb.head.kt, a.gp + b);
+    int bid = 0;
+#define HIPNLP_W8(p, s) (TERRAIN == HIPNLP_TERRAIN_PLANAR ? (p) : (s))
+#define HIPNLP_W4(p, s) (TERRAIN == HIPNLP_TERRAIN_PLANAR ? (p) : (s))
+#define DEV_R(w4, w8, fn, nt) if constexpr ((w4) == W) { for (int t_ = lane; t_ < (nt); t_ += 64) fn(cx, t_); }
+#define DEV_BARRIER lds_barrier(); if (bid == 4) fetch_tables(); bid++;
+    auto run_wave = [&](auto wc) __attribute__((always_inline)) {
+        constexpr int W = decltype(wc)::value;
+        HIPNLP_KNOT_PROGRAM(DEV_R, DEV_BARRIER)
+    };
+    // (one contiguous program instance per wave, dispatched on the wave number as a scalar, as in hipnlp_knot_kernel)
+    switch (__builtin_amdgcn_readfirstlane(wave)) {
+        case 0: run_wave(std::integral_constant<int, 0>{}); break;
+        case 1: run_wave(std::integral_constant<int, 1>{}); break;
+        case 2: run_wave(std::integral_constant<int, 2>{}); break;
+        default: run_wave(std::integral_constant<int, 3>{}); break;
+    }
+#undef DEV_R
+#undef DEV_BARRIER
+#undef HIPNLP_W8
+#undef HIPNLP_W4
+    // ---- the program has ended (its last barrier is behind it): multipliers and entry words into dead scratch, then one column per thread
+    double* ls = lgrad_lam_stage(s);
+    int32_t* lw = lgrad_word_stage(s);
+#pragma unroll
+    for (int it = 0; it < LQ; ++it) ls[tid + it * WG] = lv[it];
+#pragma unroll
+    for (int it = 0; it < LE; ++it) lw[tid + it * WG] = w[it];
+    if (tid < 16) lw[LG_ENT_CAP + tid] = wg;
+    lds_barrier();
+    constexpr int32_t SLOT = (1 << LG_SLOT_BITS) - 1;
+    auto lam_at = [&](int e) __attribute__((always_inline)) { return ls[lw[e] >> LG_SLOT_BITS]; };
+    auto jac_at = [&](int e) __attribute__((always_inline)) { return s.jac[lw[e] & SLOT]; };
+    int bad = 0;
+    if (tid < NXK) {
+        const double xb = lgrad_column(sig, s.grad[tid], e0, e1, lam_at, jac_at);
+        bad = !isfinite(xb);
+        a.out[int64_t(b) * a.n + int64_t(NXK) * k + tid] = xb;
+    } else if (last && tid >= LG_SPAN_GLOB && tid < LG_SPAN_GLOB + NXG) {   // the global variables carry no cost
+        const double xb = lgrad_column(sig, 0.0, e0, e1, lam_at, jac_at);
+        bad = !isfinite(xb);
+        a.out[int64_t(b) * a.n + int64_t(NXK) * N + (tid - LG_SPAN_GLOB)] = xb;
+    }
+    if (__any(bad) && lane == 0) atomicMax(a.flag + b, a.seq);   // generation flag: nothing to reset between launches
+}
+
 
 // Throughput variant only (4 waves; the latency variant sums inside the knot kernel, see pub_step): f[b] = sum over knots and
 // terms, cost_terms[b][t] = sum over knots.  One workgroup per trajectory.  Thread (group g = tid / 16, column c = tid % 16) sums
@@ -1346,6 +1500,7 @@ struct hipnlp_handle {
     double* d_htrash = nullptr;   // [nk * batch] DIRECT Hessian launches: one word per workgroup (HArgs::trash)
     double* hd_hess = nullptr;   // device-visible address of h_hess
     int32_t hseq = 0;   // Hessian launches so far (generation of d_hflag)
+    LgradTables* d_lt = nullptr;   // Lagrangian gradient (hipnlp_eval_lagrangian_grad_device): its tables, uploaded at the first call
     std::string err;
 };
 
@@ -1371,7 +1526,7 @@ static void free_all(hipnlp_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->dev);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* dptrs[] = {h->d_tb, h->d_ctpl, h->d_ctpl_of_b, h->d_healed, h->d_x, h->d_pk, h->d_cost_knot, h->d_gp, h->d_cost_pub, h->d_out, h->d_ht, h->d_sigma, h->d_hess, h->d_hflag, h->d_htrash};
+    void* dptrs[] = {h->d_tb, h->d_ctpl, h->d_ctpl_of_b, h->d_healed, h->d_x, h->d_pk, h->d_cost_knot, h->d_gp, h->d_cost_pub, h->d_out, h->d_ht, h->d_sigma, h->d_hess, h->d_hflag, h->d_htrash, h->d_lt};
     for (void* q : dptrs) if (q) (void)hipFree(q);
     void* hptrs[] = {h->h_x, h->h_out, h->h_hess, h->h_hflag, h->h_sl};
     for (void* q : hptrs) if (q) (void)hipHostFree(q);
@@ -2560,6 +2715,74 @@ int hipnlp_eval_hess_device(hipnlp_handle* h, const double* x_dev, const double*
     if (rc != HIPNLP_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->dev));
     return hess_launch(h, x_dev, obj_factor_dev, lambda_dev, hess_dev, stream ? hipStream_t(stream) : h->stream);
+}
+
+// ---- Lagrangian gradient sigma grad f + J^T lambda (include/hipnlp.h) ----------------------------------------------------------------
+static int lgrad_prepare(hipnlp_handle* h) {
+    if (h->d_lt) return HIPNLP_OK;
+    const Layout& L = h->L;
+    if (!L.lgrad_ok) { h->err = "hipnlp_eval_lagrangian_grad_device: " + L.lgrad_error; return HIPNLP_E_UNSUPPORTED; }
+    LgradTables* t = new LgradTables();
+    std::memset(t, 0, sizeof(LgradTables));
+    for (int v = 0; v < 3; ++v) {
+        auto word = [](const LgradEntry& e) { return int32_t(e.slot | (e.lam << LG_SLOT_BITS)); };
+        for (int i = 0; i < LG_ENT_CAP + 16; ++i) t->word[v][i] = -1;
+        for (size_t i = 0; i < L.lg_ent[v].size(); ++i) t->word[v][i] = word(L.lg_ent[v][i]);
+        for (int c = 0; c < NXK && !L.lg_cbeg[v].empty(); ++c) { t->beg[v][c] = L.lg_cbeg[v][size_t(c)]; t->end[v][c] = L.lg_cbeg[v][size_t(c) + 1]; }
+        for (int q = 0; q < LG_LAM_CAP; ++q) {
+            const bool on = q < int(L.lg_rows[v].size());
+            t->row_a[v][q] = on ? L.lg_rows[v][size_t(q)].first : G_NONE;
+            t->row_b[v][q] = on ? L.lg_rows[v][size_t(q)].second : 0;
+        }
+    }
+    static_assert(NXG <= 16, "horizon-global entry words");
+    if (L.lg_glob.size() > 16) { delete t; h->err = "hipnlp_eval_lagrangian_grad_device: more than 16 entries in the horizon-global columns"; return HIPNLP_E_UNSUPPORTED; }
+    for (size_t i = 0; i < L.lg_glob.size(); ++i) t->word[VAR_LAST][LG_ENT_CAP + i] = int32_t(L.lg_glob[i].slot | (L.lg_glob[i].lam << LG_SLOT_BITS));
+    for (int c = 0; c < NXG; ++c) { t->beg[VAR_LAST][LG_SPAN_GLOB + c] = LG_ENT_CAP + L.lg_gcbeg[size_t(c)]; t->end[VAR_LAST][LG_SPAN_GLOB + c] = LG_ENT_CAP + L.lg_gcbeg[size_t(c) + 1]; }
+    HIP_TRY(h, hipSetDevice(h->dev));
+    hipError_t e = hipMalloc(&h->d_lt, sizeof(LgradTables));
+    if (e == hipSuccess) e = hipnlp_internal_memcpy(h->d_lt, t, sizeof(LgradTables), hipMemcpyHostToDevice);
+    delete t;
+    if (e != hipSuccess) {
+        if (h->d_lt) (void)hipFree(h->d_lt);
+        h->d_lt = nullptr;
+        h->err = std::string("Lagrangian gradient tables: ") + hipGetErrorString(e);
+        return HIPNLP_E_NODEVICE;
+    }
+    return HIPNLP_OK;
+}
+int hipnlp_eval_lagrangian_grad_device(hipnlp_handle* h, const double* x_dev, const double* obj_factor_dev, const double* lambda_dev, double* out_dev, void* stream) {
+    if (!h || !x_dev || !obj_factor_dev || !lambda_dev || !out_dev) return HIPNLP_E_INVALID;
+    NOT_FRONT(h, "hipnlp_eval_lagrangian_grad_device");
+    if (h->kb != 0 || h->ke != h->L.N) {
+        h->err = "hipnlp_eval_lagrangian_grad_device: a shard handle (knot_begin / knot_end not the whole horizon) — the gradient needs every knot";
+        return HIPNLP_E_UNSUPPORTED;
+    }
+    if (!h->params_set) { h->err = "parameters not set (hipnlp_set_params)"; return HIPNLP_E_PARAMS; }
+    const int rc = lgrad_prepare(h);
+    if (rc != HIPNLP_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->dev));
+    h->have_result = false;
+    hipStream_t s = stream ? hipStream_t(stream) : h->stream;
+    if (h->seq == INT32_MAX) {   // (the launch number is the generation of the non-finite flags: start over before it wraps, as launch() does)
+        HIP_TRY(h, hipStreamSynchronize(s));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        HIP_TRY(h, hipMemset(h->d_flag, 0, size_t(h->batch) * sizeof(int32_t)));
+        std::memset(h->h_flag, 0, size_t(h->batch) * sizeof(int32_t));
+        if (h->d_cost_pub) HIP_TRY(h, hipMemset(h->d_cost_pub, 0, 2 * size_t(h->batch) * size_t(h->nk) * NCT * 2 * sizeof(unsigned long long)));
+        HIP_TRY(h, hipDeviceSynchronize());
+        h->seq = 0;
+        h->seq_result = -1;
+    }
+    LArgs a;
+    a.tb = h->d_tb; a.lt = h->d_lt; a.x = x_dev; a.pk = h->d_pk; a.gp = h->d_gp;
+    a.sigma = obj_factor_dev; a.lambda = lambda_dev; a.out = out_dev; a.flag = h->d_flag;
+    a.N = h->L.N; a.n = h->L.n; a.m = h->L.m; a.seq = ++h->seq;
+    const dim3 grid(unsigned(h->nk), unsigned(h->batch));
+    if (h->d.settings.terrain == HIPNLP_TERRAIN_PLANAR) hipLaunchKernelGGL(hipnlp_knot_lgrad_kernel<HIPNLP_TERRAIN_PLANAR>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(hipnlp_knot_lgrad_kernel<HIPNLP_TERRAIN_SMOOTH_STEPS>, grid, dim3(256), 0, s, a);
+    HIP_TRY(h, hipGetLastError());
+    return HIPNLP_OK;
 }
 // how a handle in auto mode (hipnlp_set_hessian_early_run(h, -1)) came to its choice
 enum { HESS_WHY_UNDECIDED = 0, HESS_WHY_FORCED = 1, HESS_WHY_NOT_ARMABLE = 2, HESS_WHY_NUMA_SAME = 3, HESS_WHY_NUMA_OTHER = 4, HESS_WHY_MEASURED = 5 };

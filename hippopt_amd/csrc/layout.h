@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "knot_body.h"
+#include "knot_lgrad.h"
 
 namespace hipnlp {
 
@@ -141,6 +142,16 @@ struct Layout {
     // hipnlp_create launches no VARY kernel for a layout that fails it (tests/test_constant_jacobian.py asserts it holds).
     bool vary_partition_ok = false;
     int vary_slot_min = -1, vary_slot_max = -1;   // smallest / largest recorded slot that depends on x
+    // Lagrangian gradient (knot_lgrad.h, hipnlp_eval_lagrangian_grad_device): the entries of a variant-v block in (column, row) order
+    // whatever the jac order, lg_cbeg[v][c] .. lg_cbeg[v][c + 1] those of column c; lg_rows[v] the rows they touch, {row_a, row_b} at the
+    // position LgradEntry::lam (the knot's own rows, the trapezoid-defect rows of knot k + 1; for the last knot also the rows of the
+    // horizon-global entries).  lg_glob: the entries of the horizon-global columns (jperm_glob; rows resolved at knot 0, row_b = 0),
+    // written by the last knot, whose multiplier list they index.  lgrad_ok: the tables fit the device kernel's staging (else lgrad_error).
+    std::vector<LgradEntry> lg_ent[3], lg_glob;
+    std::vector<int32_t> lg_cbeg[3], lg_gcbeg;
+    std::vector<std::pair<int32_t, int32_t>> lg_rows[3];
+    bool lgrad_ok = false;
+    std::string lgrad_error;
     std::vector<int32_t> irow, jcol;      // full pattern, CCS order
     std::string error;
 
@@ -325,8 +336,18 @@ struct Layout {
             }
         }
         // ---- jac tables: CCS order inside the column block of a knot ------------------------------------
+        // (row stride of the block behind a row id: the row at knot k is affine in k, as for the g tables above)
+        auto row_stride = [&](int rid) {
+            const int bi = blk[rid_kind(rid)][rid_point(rid)];
+            return blocks[size_t(bi)].nk > 1 ? (lifted ? blocks[size_t(bi)].kept : blocks[size_t(bi)].rows) : 0;
+        };
         jperm_glob.clear();
+        lg_glob.clear();
+        lg_gcbeg.assign(NXG + 1, 0);
         for (int v = 0; v < 3; ++v) {
+            lg_ent[v].clear();
+            lg_cbeg[v].assign(NXK + 1, 0);
+            lg_rows[v].clear();
             jperm[v].clear();
             nnz_v[v] = 0;
             if (v == VAR_INTERIOR && N < 3) continue;
@@ -341,6 +362,21 @@ struct Layout {
             std::sort(ent.begin(), ent.end());
             for (size_t i = 1; i < ent.size(); ++i)
                 if (ent[i].first == ent[i - 1].first) { error = "internal: duplicate jacobian entry"; return false; }
+            {   // Lagrangian gradient tables: (column, row) order, before a varying-first partition
+                auto lam_pos = [&](int ra, int rb) {
+                    for (size_t q = 0; q < lg_rows[v].size(); ++q) if (lg_rows[v][q] == std::make_pair(ra, rb)) return int(q);
+                    lg_rows[v].push_back({ra, rb});
+                    return int(lg_rows[v].size()) - 1;
+                };
+                for (auto& e : ent) {
+                    const int slot = e.second, r = e.first.second, rb = row_stride(jrid[size_t(slot)]);
+                    const int ra = r - rb * krep[v];
+                    lg_ent[v].push_back({slot, e.first.first, ra, rb, lam_pos(ra, rb)});
+                }
+                lg_cbeg[v].assign(NXK + 1, 0);
+                for (auto& e : lg_ent[v]) lg_cbeg[v][size_t(e.col) + 1]++;
+                for (int c = 0; c < NXK; ++c) lg_cbeg[v][size_t(c) + 1] += lg_cbeg[v][size_t(c)];
+            }
             if (vary_first)   // (stable: CCS order within the varying entries and within the constant ones)
                 std::stable_partition(ent.begin(), ent.end(), [&](const std::pair<std::pair<int, int>, int>& e) { return !jconst_slot[size_t(e.second)]; });
             jconst_pos[v].clear();
@@ -359,6 +395,24 @@ struct Layout {
                 }
             }
         }
+        // horizon-global columns: summed by the last knot, their rows (resolved at knot 0) behind that knot's own multipliers
+        for (int slot : jperm_glob) {
+            const int r = resolve(jrid[size_t(slot)], 0);
+            int q = 0;
+            while (q < int(lg_rows[VAR_LAST].size()) && lg_rows[VAR_LAST][size_t(q)] != std::make_pair(r, 0)) ++q;
+            if (q == int(lg_rows[VAR_LAST].size())) lg_rows[VAR_LAST].push_back({r, 0});
+            lg_glob.push_back({slot, jc[size_t(slot)] - COL_GLOBAL, r, 0, q});
+            lg_gcbeg[size_t(jc[size_t(slot)] - COL_GLOBAL) + 1]++;
+        }
+        for (int c = 0; c < NXG; ++c) lg_gcbeg[size_t(c) + 1] += lg_gcbeg[size_t(c)];
+        lgrad_ok = true;
+        lgrad_error.clear();
+        for (int v = 0; v < 3; ++v)
+            if (int(lg_ent[v].size()) > LG_ENT_CAP || int(lg_rows[v].size()) > LG_LAM_CAP) {
+                lgrad_ok = false;
+                lgrad_error = "a knot block of jac g has " + std::to_string(lg_ent[v].size()) + " entries in " + std::to_string(lg_rows[v].size()) +
+                              " rows: more than the Lagrangian-gradient kernel stages (" + std::to_string(LG_ENT_CAP) + " / " + std::to_string(LG_LAM_CAP) + ")";
+            }
         jac_glob_base = int(jac_base(N - 1)) + nnz_v[VAR_LAST];
         nnz = jac_glob_base + int(jperm_glob.size());
         // ---- full pattern ---------------------------------------------------------------------------------

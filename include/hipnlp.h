@@ -419,6 +419,19 @@ int hipnlp_eval_device(hipnlp_handle* h, const double* x_dev,
                        double* f_dev, double* grad_dev, double* g_dev, double* jac_dev,
                        void* stream);
 
+/* Gradient of the Lagrangian  out = obj_factor grad f(x) + J(x)^T lambda,  per trajectory: the vector a device-side consumer of a batch
+ * needs to differentiate a scalar built from f and g (a training loss over the trajectories, a penalty or augmented-Lagrangian merit, the
+ * backward pass of hippopt_amd.autograd).  Shapes and stream rules of hipnlp_eval_hess_device: x_dev [batch][n], obj_factor_dev [batch],
+ * lambda_dev [batch][m] (m of THIS handle: the reduced rows of a HIPNLP_FLAG_DETECT_SIMPLE_BOUNDS handle), out_dev [batch][n]; device
+ * pointers, enqueued on `stream` (NULL = the handle's own), not synchronised.  ONE launch: every knot sums the columns of its own block
+ * of jac g — 189 doubles leave per knot instead of the 1 849 of f, grad f, g and jac g; no value of jac g reaches memory.
+ * Each column is summed in (column, row) order whatever the handle's jac order: CCS and varying-first handles give the same bits.  A
+ * NaN / Inf in the result raises the handle's non-finite flag, as hipnlp_eval_device does.
+ * Returns HIPNLP_E_PARAMS before hipnlp_set_params; HIPNLP_E_UNSUPPORTED on a multi-device handle and on a shard handle (knot_begin /
+ * knot_end not the whole horizon), hipnlp_last_error says which. */
+int hipnlp_eval_lagrangian_grad_device(hipnlp_handle* h, const double* x_dev, const double* obj_factor_dev, const double* lambda_dev,
+                                       double* out_dev, void* stream);
+
 /* Sharded variant (multi-GPU): the handle owns knots [knot_begin, knot_end).  Outputs are
  * shard-local and contiguous so that one RCCL all-gather reassembles them:
  *   grad_shard [batch][shard_grad]  = grad f entries of the shard's knots (+ the 6 global entries on the last shard)
