@@ -6,9 +6,20 @@
     loss = a * f.sum() + (w * g).sum()
     loss.backward()                                        # x.grad = a grad f + J^T w, ONE launch (hipnlp_eval_lagrangian_grad_device)
 
+    hv = nlp.hessian_vector_product(x, sigma, lam, v)      # H(x, sigma, lam) v, ONE launch (hipnlp_eval_hess_vec_device), H never written
+    H = nlp.hessian(x, sigma, lam)                         # the value run [B, nnz_h] (hipnlp_eval_hess_device), for many products at one x
+    hv = H.matvec(v)                                       # hipnlp_hess_times_device: bit for bit the fused product
+
 The forward pass is hipnlp_eval_device with grad f and jac g left out; the backward pass is the Lagrangian gradient
 sigma grad f + J^T lambda with sigma = df, lambda = dg (zeros for an output whose gradient is None): the Jacobian never reaches memory.
-Both run on torch.cuda.current_stream().  Not twice differentiable (once_differentiable); no derivative with respect to the parameters.
+All launches run on torch.cuda.current_stream().
+
+Second derivatives in x: the Lagrangian gradient is itself a differentiable function of x whose backward pass is the Hessian-vector
+product.  lagrangian_gradient(x, ...) with x.requires_grad, and loss.backward(create_graph=True) / torch.autograd.grad(...,
+create_graph=True) through nlp(x), record it; without create_graph the backward pass is exactly the one launch above.  The derivatives
+of the Lagrangian gradient with respect to sigma and lam are grad f . w and J w: the engine has no Jacobian-vector product, so a double
+backward that needs them — a loss that is not linear in f and g, e.g. (f ** 2).sum(), or a sigma / lam that requires grad — raises
+NotImplementedError instead of returning zeros.  No third derivative; no derivative with respect to the parameters.
 torch is imported when first needed."""
 import numbers
 
@@ -17,6 +28,7 @@ import numpy as np
 from .hipnlp import HipNlp
 
 _FUNCTION = None
+_LGRAD_FUNCTION = None
 
 
 def _torch():
@@ -29,7 +41,6 @@ def _function():
     global _FUNCTION
     if _FUNCTION is None:
         torch = _torch()
-        from torch.autograd.function import once_differentiable
 
         class NLPFunction(torch.autograd.Function):
             @staticmethod
@@ -42,16 +53,64 @@ def _function():
                 return f, g
 
             @staticmethod
-            @once_differentiable
             def backward(ctx, df, dg):
                 (x,) = ctx.saved_tensors
                 nlp = ctx.nlp
                 sigma = df.to(torch.float64).contiguous() if df is not None else torch.zeros(nlp.batch, dtype=torch.float64, device=x.device)
                 lam = dg.to(torch.float64).contiguous() if dg is not None else torch.zeros(nlp.batch, nlp.m, dtype=torch.float64, device=x.device)
+                if torch.is_grad_enabled():   # (create_graph=True: the same launch, recorded, so that it can be differentiated in x)
+                    return _lgrad_function().apply(x, sigma, lam, nlp), None
                 return nlp._launch(x, sigma, lam), None
 
         _FUNCTION = NLPFunction
     return _FUNCTION
+
+
+def _lgrad_function():
+    """the Lagrangian gradient as a torch.autograd.Function of (x, sigma, lam): its backward pass in x is the Hessian-vector product"""
+    global _LGRAD_FUNCTION
+    if _LGRAD_FUNCTION is None:
+        torch = _torch()
+        from torch.autograd.function import once_differentiable
+
+        class LagrangianGradFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x, sigma, lam, nlp):
+                ctx.save_for_backward(x, sigma, lam)
+                ctx.nlp = nlp
+                return nlp._launch(x.detach(), sigma.detach(), lam.detach())
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, w):
+                x, sigma, lam = ctx.saved_tensors
+                if ctx.needs_input_grad[1]:
+                    raise NotImplementedError("the derivative of the Lagrangian gradient with respect to sigma is grad f . w: the engine has no "
+                                              "such product (a loss that is not linear in f, or a sigma that requires grad)")
+                if ctx.needs_input_grad[2]:
+                    raise NotImplementedError("the derivative of the Lagrangian gradient with respect to lam is the Jacobian-vector product J w: "
+                                              "the engine has none (a loss that is not linear in g, or a lam that requires grad)")
+                gx = ctx.nlp._launch_hvp(x, sigma, lam, w.to(torch.float64).contiguous()) if ctx.needs_input_grad[0] else None
+                return gx, None, None, None
+
+        _LGRAD_FUNCTION = LagrangianGradFunction
+    return _LGRAD_FUNCTION
+
+
+class HessianValues:
+    """The Hessian of the Lagrangian of every trajectory at one (x, sigma, lam), as the value run `values` [batch, nnz_h] of
+    hipnlp_eval_hess_device (pattern: engine.hess_sparsity()); matvec(v) multiplies it by v [batch, n] in one launch
+    (hipnlp_hess_times_device) — what the inner iterations of a CG solve at fixed x call."""
+
+    def __init__(self, nlp, values):
+        self.nlp, self.values = nlp, values
+
+    def matvec(self, v):
+        nlp = self.nlp
+        nlp._check("v", v, (nlp.batch, nlp.n))
+        out = _torch().empty_like(v, memory_format=_torch().contiguous_format)
+        nlp._on_current_stream(lambda s: nlp.engine.hess_times_device(self.values.data_ptr(), v.data_ptr(), out.data_ptr(), stream=s))
+        return out
 
 
 class KinodynamicNLP:
@@ -86,7 +145,34 @@ class KinodynamicNLP:
             sigma = torch.full((self.batch,), float(sigma), dtype=torch.float64, device=self.device)
         self._check("sigma", sigma, (self.batch,))
         self._check("lam", lam, (self.batch, self.m))
+        if x.requires_grad and torch.is_grad_enabled():   # (differentiable in x: the backward pass is the Hessian-vector product)
+            return _lgrad_function().apply(x, sigma, lam, self)
         return self._launch(x, sigma, lam)
+
+    def _sigma(self, sigma):
+        if isinstance(sigma, numbers.Real):
+            sigma = _torch().full((self.batch,), float(sigma), dtype=_torch().float64, device=self.device)
+        self._check("sigma", sigma, (self.batch,))
+        return sigma
+
+    def hessian_vector_product(self, x, sigma, lam, v):
+        """H(x, sigma, lam) v per trajectory ([batch, n]), H the Hessian of sigma f + lam . g in x: sigma a number or a [batch] tensor,
+        lam [batch, m], v [batch, n].  One launch; H is never written.  Not recorded by autograd."""
+        self._check("x", x, (self.batch, self.n))
+        sigma = self._sigma(sigma)
+        self._check("lam", lam, (self.batch, self.m))
+        self._check("v", v, (self.batch, self.n))
+        return self._launch_hvp(x, sigma, lam, v)
+
+    def hessian(self, x, sigma, lam):
+        """HessianValues at (x, sigma, lam): one hipnlp_eval_hess_device launch; .matvec(v) is bit for bit hessian_vector_product(..., v)"""
+        torch = _torch()
+        self._check("x", x, (self.batch, self.n))
+        sigma = self._sigma(sigma)
+        self._check("lam", lam, (self.batch, self.m))
+        values = torch.empty(self.batch, self.engine.hess_nnz(), dtype=torch.float64, device=self.device)
+        self._on_current_stream(lambda s: self.engine.eval_hess_device(x.data_ptr(), sigma.data_ptr(), lam.data_ptr(), values.data_ptr(), stream=s))
+        return HessianValues(self, values)
 
     # ---- internals ------------------------------------------------------------------------------------------------------------------
     def _on_current_stream(self, launch):
@@ -110,6 +196,11 @@ class KinodynamicNLP:
     def _launch(self, x, sigma, lam):
         out = _torch().empty_like(x, memory_format=_torch().contiguous_format)
         self._on_current_stream(lambda s: self.engine.eval_lagrangian_grad_device(x.data_ptr(), sigma.data_ptr(), lam.data_ptr(), out.data_ptr(), stream=s))
+        return out
+
+    def _launch_hvp(self, x, sigma, lam, v):
+        out = _torch().empty_like(x, memory_format=_torch().contiguous_format)
+        self._on_current_stream(lambda s: self.engine.eval_hess_vec_device(x.data_ptr(), sigma.data_ptr(), lam.data_ptr(), v.data_ptr(), out.data_ptr(), stream=s))
         return out
 
     def _check(self, name, t, shape):

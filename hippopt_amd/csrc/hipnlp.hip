@@ -1087,6 +1087,241 @@ void hipnlp_knot_hess_kernel(HArgs a) {
 }
 
 // =====================================================================================================================
+// Hessian-vector product  y = H(x, sigma, lambda) v  (hipnlp_eval_hess_vec_device, hipnlp_hess_times_device).  The Hessian is block
+// diagonal by knot, so knot k's 189 elements of y are sums over entries knot k's workgroup holds: the fused kernel runs what
+// hipnlp_knot_hess_kernel<TERRAIN, LAYOUT_COMPACT> runs — the same program, the same emitter, hx.H in LDS — and then, instead of the
+// copy-out of the block, sums one variable per thread (knot_hvp.h) over the touch lists of HessLayout: 189 doubles leave per knot, not
+// 1 539 / 1 878, and H is never written.  The touch words and this knot's record of v are fetched behind the fifth barrier (where the
+// Hessian kernel fetches its copy-out permutation) and staged, once the program has ended, over the knot scratch: every member of it is
+// dead by then (s.g holds only multipliers, the rest is kinematics), only hx.H is read.  The stored-values kernel does the same sums
+// from a value run hipnlp_eval_hess_device wrote: values by block position, the same lists, the same order — the same bits.
+// =====================================================================================================================
+constexpr int HVP_SPAN_GLOB = 192;   // threads 192 .. 192 + NXG - 1 of the last knot write the (zero) horizon-global elements
+static_assert(NXK <= HVP_SPAN_GLOB && HVP_SPAN_GLOB + NXG <= 256, "hvp variable threads");
+struct alignas(16) HvpTables {
+    int32_t word_slot[HVP_WORD_CAP];   // touch e: native slot | other variable << HVP_IDX_BITS   (fused kernel; 0 behind the last touch)
+    int32_t word_pos[HVP_WORD_CAP];    // touch e: position in the knot block | other variable << HVP_IDX_BITS   (stored values)
+    int32_t row[256];                  // variable i: first touch | touches << HVP_IDX_BITS | coupled << HVP_COUPLED_BIT   (0 behind NXK)
+    int32_t couple[256];               // variable i: its coupling entry (index behind the knot blocks of a value run), -1: none
+};
+struct VArgs {
+    const DeviceTables* tb;
+    const HessTables* ht;
+    const HvpTables* vt;
+    const double* x;        // [batch][n]
+    const double* pk;
+    const GParams* gp;
+    const double* sigma;    // [batch]
+    const double* lambda;   // [batch][m]
+    const double* v;        // [batch][n]
+    double* out;            // [batch][n]
+    int32_t* flag;          // [batch] the handle's Hessian non-finite flag (== seq after a launch that produced one)
+    int32_t N, n, m, seq, n_couple;
+};
+constexpr int HVP_WORDS_PER_THREAD = HVP_WORD_CAP / 256;
+// one variable per thread over staged touch words `tw` and the staged record `vs` of v; val(idx): the entry behind a word's low bits
+template <class Val> __device__ __forceinline__ double hvp_thread_row(int32_t row, const int32_t* tw, const double* vs, const Val& val, double c, double v_other_end) {
+    constexpr int32_t IDX = (1 << HVP_IDX_BITS) - 1, CNT = (1 << HVP_CNT_BITS) - 1;
+    const int beg = row & IDX, end = beg + ((row >> HVP_IDX_BITS) & CNT);
+    return hvp_row(beg, end, [&](int e) __attribute__((always_inline)) { return val(tw[e] & IDX); },
+                   [&](int e) __attribute__((always_inline)) { return vs[tw[e] >> HVP_IDX_BITS]; }, ((row >> HVP_COUPLED_BIT) & 1) != 0, c, v_other_end);
+}
+template <int TERRAIN> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3)))
+void hipnlp_knot_hvp_kernel(VArgs a) {
+    using Em = DevEmH<TERRAIN, LAYOUT_COMPACT, false>;   // (the staged compact Hessian kernel's emitter: the same program, the same bits of H)
+    using Scratch = typename Em::Scratch;
+    static_assert(Scratch::compact, "the compact scratch of the batch Hessian kernel");
+    static_assert(offsetof(Scratch, jac) + sizeof(Scratch::jac) + 16 > sizeof(Scratch) && offsetof(Scratch, grad) + sizeof(Scratch::grad) == offsetof(Scratch, jac),
+                  "grad and jac are the last members of the scratch (up to tail padding)");
+    constexpr size_t S_BYTES = offsetof(Scratch, grad);
+    static_assert(S_BYTES % 16 == 0, "scratch prefix");
+    constexpr int WG = 256;
+    __shared__ alignas(16) double s_raw[S_BYTES / sizeof(double)];
+    Scratch& s = *reinterpret_cast<Scratch*>(s_raw);
+    __shared__ SharedTablesT<true> tabs;
+    __shared__ alignas(16) double hx_raw[sizeof(KHessScratch) / sizeof(double)];
+    KHessScratch& hx = *reinterpret_cast<KHessScratch*>(hx_raw);
+    static_assert(S_BYTES + sizeof(SharedTablesT<true>) + sizeof(KHessScratch) <= 160 * 1024 / 3, "three workgroups per CU");
+    // once the program has ended the touch words and the record of v lie on the knot scratch, from its first member on (Jr / own, g, x, xm,
+    // xg, pk and the kinematic arrays up to grad): all of it dead behind the program's last barrier, none of it part of hx
+    constexpr size_t TW_BYTES = HVP_WORD_CAP * sizeof(int32_t), VS_BYTES = XPAD * sizeof(double);
+    static_assert(TW_BYTES % 16 == 0 && TW_BYTES + VS_BYTES <= S_BYTES && NXK <= XPAD, "touch words and v on the dead knot scratch");
+    static_assert(offsetof(Scratch, g) + sizeof(Scratch::g) <= S_BYTES && offsetof(Scratch, comp) + sizeof(Scratch::comp) <= S_BYTES, "the staging stays inside the allocated prefix");
+    constexpr int G_USED = gs::FIN;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int b = blockIdx.y;
+    const int k = int((blockIdx.x & 7u) * (gridDim.x >> 3) + min(blockIdx.x & 7u, gridDim.x & 7u) + (blockIdx.x >> 3));   // (XCD-aware, as in hipnlp_knot_kernel)
+    const int N = a.N;
+    const int first = k == 0, last = k == N - 1;
+    const double* x = a.x + size_t(b) * a.n;
+    const DeviceTables& tb = *a.tb;
+    double sig = 0.0;
+    {
+        // staged as in hipnlp_knot_hess_kernel: records and tables straight from global memory into LDS, 1 KB chunks dealt over the waves
+        constexpr int WAVES = WG / 64;
+        constexpr int XB = NXK * 8 / 16 * 16, XREM = NXK - XB / 8;
+        const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+        int rot = 0;
+        auto stage = [&](const void* src, void* dst, int bytes) __attribute__((always_inline)) {
+            for (int r0 = 0; r0 < bytes; r0 += WG * 16) {
+                const int wv = (wave_u + WAVES - rot % WAVES) & (WAVES - 1);
+                const int off = r0 + wv * 1024 + lane * 16;
+                if (off < bytes)
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(static_cast<const char*>(src) + off),
+                                                     (__attribute__((address_space(3))) void*)(static_cast<char*>(dst) + r0 + wv * 1024), 16, 0, 0);
+                rot += ((bytes - r0 < WG * 16 ? bytes - r0 : WG * 16) + 1023) / 1024;
+            }
+        };
+        const double* lam = a.lambda + size_t(b) * a.m;
+        const int v = first ? VAR_FIRST : (last ? VAR_LAST : VAR_INTERIOR);
+        constexpr int LG_ITERS = (gs::COUNT + WG - 1) / WG;
+        int lga[LG_ITERS], lgb[LG_ITERS];
+#pragma unroll
+        for (int it = 0; it < LG_ITERS; ++it) { lga[it] = tb.g_a[v][tid + it * WG]; lgb[it] = tb.g_b[tid + it * WG]; }   // (padded tables)
+        int nga = G_NONE, ngb = 0;
+        if (tid < 3 && k + 1 < N) { const int slot = gs::HDYN + 3 + tid; nga = tb.g_a[k + 1 == N - 1 ? VAR_LAST : VAR_INTERIOR][slot]; ngb = tb.g_b[slot]; }
+        sig = a.sigma[b];
+        stage(x + size_t(NXK) * k, s.x, XB);
+        if (!first) stage(x + size_t(NXK) * (k - 1), s.xm, XB); else rot += (XB + 1023) / 1024;
+        stage(a.pk + (size_t(b) * N + k) * PK_STRIDE, s.pk, PK_STRIDE * 8);
+        stage(x + size_t(NXK) * N, s.xg, NXG * 8);
+        stage(static_cast<const GParamsLite*>(a.gp + b), &tabs.gp, int(sizeof(GParamsLite)));
+        stage(&tb.head.ks, &tabs.ks, int(sizeof(KSettings)));
+        stage(static_cast<const KinLite*>(&tb.head.kt), &tabs.kt, int(sizeof(KinLite)));
+        stage(&a.ht->far, &hx.far, int(sizeof(KHFarLists)));
+        double xrem = 0.0, xov = 0.0;
+        if (XREM && tid < 2 && !(first && tid == 1)) xrem = x[size_t(NXK) * (k - tid) + XB / 8];
+        if (first || last) { if (tid < NPER) xov = x[size_t(NXK) * (first ? N - 1 : 0) + periodicity_row_var(tid)]; }
+        double lv[LG_ITERS];
+#pragma unroll
+        for (int it = 0; it < LG_ITERS; ++it) lv[it] = lga[it] != G_NONE ? lam[lga[it] + lgb[it] * k] : 0.0;
+        const double lnext = nga != G_NONE ? lam[nga + ngb * (k + 1)] : 0.0;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the staging loads of THIS wave have landed in LDS
+        if (first || last) { if (tid < NPER) s.xo[tid] = xov; }
+        if (XREM && tid < 2) (tid ? s.xm : s.x)[XB / 8] = xrem;
+        if (first) { for (int i = tid; i < XB / 8; i += WG) s.xm[i] = 0.0; }
+        if (tid >= 64 && tid < 64 + XPAD - NXK) { s.x[NXK + tid - 64] = 0.0; s.xm[NXK + tid - 64] = 0.0; }
+        if (tid >= 128 && tid < 128 + 8 - NXG) s.xg[NXG + tid - 128] = 0.0;
+#pragma unroll
+        for (int it = 0; it < LG_ITERS; ++it) { const int slot = tid + it * WG; if (slot < G_USED) s.g[slot] = lv[it]; }
+        if (tid < 3) hx.lam_next[tid] = lnext;
+        if (tid == 0) hx.sigma = sig;
+    }
+    lds_barrier();
+    // the touch words, the row word of this thread's variable, its element of v and — first and last knot of a handle with the periodicity
+    // as a cost — the same variable of v at the other end of the horizon: fetched behind the fifth barrier, in flight across the last phase
+    const HvpTables& vt = *a.vt;
+    const double* vb = a.v + size_t(b) * a.n;
+    const bool ends_coupled = a.n_couple > 0 && (first || last);
+    int32_t wr[HVP_WORDS_PER_THREAD], row = 0;
+    double vk = 0.0, vo = 0.0;
+    auto fetch_tables = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int it = 0; it < HVP_WORDS_PER_THREAD; ++it) wr[it] = vt.word_slot[tid + it * WG];
+        row = vt.row[tid];
+        if (!ends_coupled) row &= ~(1 << HVP_COUPLED_BIT);   // (the coupling term belongs to the two horizon ends)
+        if (tid < NXK) {
+            vk = vb[size_t(NXK) * k + tid];
+            if (ends_coupled) vo = vb[size_t(NXK) * (first ? N - 1 : 0) + tid];
+        }
+    };
+    int bar = 0;   // barriers passed (the program is straight-line code: a constant at every use)
+    KnotInfo ki{k, N, first, last};
+    Em em{s.g, s.jac, hx.H};
+    Ctx<Em> cx(s, tabs.kin(), tabs.settings(), tabs.gp, ki, em, &tb.head.kt, a.gp + b);
+    KHCtx<Em> hcx{cx, hx, s.g};
+#define DEV_KIN(w, fn, nt) if constexpr ((w) == W) { for (int t_ = lane; t_ < (nt); t_ += 64) fn(cx, t_); }
+#define DEV_RH(w, fn, nt) if constexpr ((w) == W) { for (int t_ = lane; t_ < (nt); t_ += 64) fn(hcx, t_); }
+#define DEV_BARRIER lds_barrier(); if (++bar == HIPNLP_HESS_TABLES_AT) fetch_tables();
+    auto run_wave = [&](auto wc) __attribute__((always_inline)) {
+        constexpr int W = decltype(wc)::value;
+        HIPNLP_KNOT_HESS_PROGRAM(DEV_KIN, DEV_RH, DEV_BARRIER)
+    };
+    // (one contiguous program instance per wave, dispatched on the wave number as a scalar, as in hipnlp_knot_hess_kernel)
+    switch (__builtin_amdgcn_readfirstlane(wave)) {
+        case 0: run_wave(std::integral_constant<int, 0>{}); break;
+        case 1: run_wave(std::integral_constant<int, 1>{}); break;
+        case 2: run_wave(std::integral_constant<int, 2>{}); break;
+        default: run_wave(std::integral_constant<int, 3>{}); break;
+    }
+#undef DEV_KIN
+#undef DEV_RH
+#undef DEV_BARRIER
+    // ---- the program has ended (its last barrier is behind it): the coupling value while the settings are still there, then touch words
+    // and v over the dead knot scratch, then one variable per thread
+    const double cpl = kh_percouple_value(sig, tabs.settings().periodicity_weight);
+    int32_t* tw = reinterpret_cast<int32_t*>(s_raw);
+    double* vs = s_raw + TW_BYTES / sizeof(double);
+#pragma unroll
+    for (int it = 0; it < HVP_WORDS_PER_THREAD; ++it) tw[tid + it * WG] = wr[it];
+    if (tid < XPAD) vs[tid] = vk;
+    lds_barrier();
+    int bad = 0;
+    if (tid < NXK) {
+        const double y = hvp_thread_row(row, tw, vs, [&](int slot) __attribute__((always_inline)) { return hx.H[slot]; }, cpl, vo);
+        bad = !isfinite(y);
+        a.out[int64_t(b) * a.n + int64_t(NXK) * k + tid] = y;
+    } else if (last && tid >= HVP_SPAN_GLOB && tid < HVP_SPAN_GLOB + NXG) {   // no entry of the Hessian touches the horizon-global variables
+        a.out[int64_t(b) * a.n + int64_t(NXK) * N + (tid - HVP_SPAN_GLOB)] = 0.0;
+    }
+    if (__any(bad) && lane == 0) atomicMax(a.flag + b, a.seq);   // generation flag: nothing to reset between launches
+}
+
+// The same sums from a value run of hipnlp_eval_hess_device: one workgroup per (trajectory, knot); the knot's block, the touch words and
+// the record of v go into LDS with coalesced reads, then one variable per thread.  No x, no parameters, no multipliers.
+struct TArgs {
+    const HvpTables* vt;
+    const double* values;   // [batch][nnz_h]
+    const double* v;        // [batch][n]
+    double* out;            // [batch][n]
+    int32_t N, n, nnz_knot, n_couple;
+    int64_t nnz_h;
+};
+__global__ __launch_bounds__(256)
+void hipnlp_hess_times_kernel(TArgs a) {
+    constexpr int WG = 256;
+    constexpr int HB = (hk::COUNT + WG - 1) / WG;
+    __shared__ double hv[HB * WG];
+    __shared__ int32_t tw[HVP_WORD_CAP];
+    __shared__ double vs[XPAD];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.y, k = blockIdx.x, N = a.N;
+    const int first = k == 0, last = k == N - 1;
+    const HvpTables& vt = *a.vt;
+    const double* vals = a.values + int64_t(b) * a.nnz_h;
+    const double* blk = vals + int64_t(a.nnz_knot) * k;
+    const double* vb = a.v + size_t(b) * a.n;
+    double h[HB];
+    int32_t wr[HVP_WORDS_PER_THREAD];
+#pragma unroll
+    for (int it = 0; it < HB; ++it) { const int i = tid + it * WG; h[it] = i < a.nnz_knot ? blk[i] : 0.0; }
+#pragma unroll
+    for (int it = 0; it < HVP_WORDS_PER_THREAD; ++it) wr[it] = vt.word_pos[tid + it * WG];
+    const int32_t row = vt.row[tid];
+    double vk = 0.0, vo = 0.0, cpl = 0.0;
+    if (tid < NXK) {
+        vk = vb[size_t(NXK) * k + tid];
+        if (a.n_couple > 0 && (first || last) && ((row >> HVP_COUPLED_BIT) & 1)) {
+            vo = vb[size_t(NXK) * (first ? N - 1 : 0) + tid];
+            cpl = vals[int64_t(a.nnz_knot) * N + vt.couple[tid]];
+        }
+    }
+#pragma unroll
+    for (int it = 0; it < HB; ++it) hv[tid + it * WG] = h[it];
+#pragma unroll
+    for (int it = 0; it < HVP_WORDS_PER_THREAD; ++it) tw[tid + it * WG] = wr[it];
+    if (tid < XPAD) vs[tid] = vk;
+    __syncthreads();
+    if (tid < NXK) {
+        const bool on = a.n_couple > 0 && (first || last);
+        const double y = hvp_thread_row(on ? row : row & ~(1 << HVP_COUPLED_BIT), tw, vs, [&](int pos) __attribute__((always_inline)) { return hv[pos]; }, cpl, vo);
+        a.out[int64_t(b) * a.n + int64_t(NXK) * k + tid] = y;
+    } else if (last && tid >= HVP_SPAN_GLOB && tid < HVP_SPAN_GLOB + NXG) {
+        a.out[int64_t(b) * a.n + int64_t(NXK) * N + (tid - HVP_SPAN_GLOB)] = 0.0;
+    }
+}
+
+// =====================================================================================================================
 // Lagrangian gradient  xbar = sigma grad f(x) + J(x)^T lambda  (hipnlp_eval_lagrangian_grad_device).  Every entry of jac g whose column
 // belongs to knot k is emitted by knot k's program, so the knot's 189 columns of J^T lambda are sums over entries its workgroup holds in
 // LDS: one workgroup of four waves per (trajectory, knot) runs the knot program of the four-wave callback kernel — the same emitter, the
@@ -1501,6 +1736,7 @@ struct hipnlp_handle {
     double* hd_hess = nullptr;   // device-visible address of h_hess
     int32_t hseq = 0;   // Hessian launches so far (generation of d_hflag)
     LgradTables* d_lt = nullptr;   // Lagrangian gradient (hipnlp_eval_lagrangian_grad_device): its tables, uploaded at the first call
+    HvpTables* d_vt = nullptr;     // Hessian-vector product (hipnlp_eval_hess_vec_device, hipnlp_hess_times_device): its tables, uploaded at the first call
     std::string err;
 };
 
@@ -1526,7 +1762,7 @@ static void free_all(hipnlp_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->dev);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* dptrs[] = {h->d_tb, h->d_ctpl, h->d_ctpl_of_b, h->d_healed, h->d_x, h->d_pk, h->d_cost_knot, h->d_gp, h->d_cost_pub, h->d_out, h->d_ht, h->d_sigma, h->d_hess, h->d_hflag, h->d_htrash, h->d_lt};
+    void* dptrs[] = {h->d_tb, h->d_ctpl, h->d_ctpl_of_b, h->d_healed, h->d_x, h->d_pk, h->d_cost_knot, h->d_gp, h->d_cost_pub, h->d_out, h->d_ht, h->d_sigma, h->d_hess, h->d_hflag, h->d_htrash, h->d_lt, h->d_vt};
     for (void* q : dptrs) if (q) (void)hipFree(q);
     void* hptrs[] = {h->h_x, h->h_out, h->h_hess, h->h_hflag, h->h_sl};
     for (void* q : hptrs) if (q) (void)hipHostFree(q);
@@ -2781,6 +3017,82 @@ int hipnlp_eval_lagrangian_grad_device(hipnlp_handle* h, const double* x_dev, co
     const dim3 grid(unsigned(h->nk), unsigned(h->batch));
     if (h->d.settings.terrain == HIPNLP_TERRAIN_PLANAR) hipLaunchKernelGGL(hipnlp_knot_lgrad_kernel<HIPNLP_TERRAIN_PLANAR>, grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL(hipnlp_knot_lgrad_kernel<HIPNLP_TERRAIN_SMOOTH_STEPS>, grid, dim3(256), 0, s, a);
+    HIP_TRY(h, hipGetLastError());
+    return HIPNLP_OK;
+}
+// ---- Hessian-vector product H(x, sigma, lambda) v (include/hipnlp.h) -------------------------------------------------------------------
+static int hvp_prepare(hipnlp_handle* h, const char* who) {
+    const int rc = hess_prepare(h);
+    if (rc != HIPNLP_OK) return rc;
+    if (h->d_vt) return HIPNLP_OK;
+    const HessLayout& HL = h->HL;
+    if (!HL.hvp_ok) { h->err = std::string(who) + ": " + HL.hvp_error; return HIPNLP_E_UNSUPPORTED; }
+    HvpTables* t = new HvpTables();
+    std::memset(t, 0, sizeof(HvpTables));
+    for (size_t e = 0; e < HL.hv_touch.size(); ++e) {
+        t->word_slot[e] = int32_t(HL.hv_touch[e].slot | (HL.hv_touch[e].other << HVP_IDX_BITS));
+        t->word_pos[e] = int32_t(HL.hv_touch[e].pos | (HL.hv_touch[e].other << HVP_IDX_BITS));
+    }
+    for (int i = 0; i < 256; ++i) t->couple[i] = -1;
+    for (int i = 0; i < NXK; ++i) {
+        t->couple[i] = HL.hv_couple[size_t(i)];
+        t->row[i] = int32_t(HL.hv_beg[size_t(i)] | (HL.hv_K[size_t(i)] << HVP_IDX_BITS) | ((HL.hv_couple[size_t(i)] >= 0 ? 1 : 0) << HVP_COUPLED_BIT));
+    }
+    HIP_TRY(h, hipSetDevice(h->dev));
+    hipError_t e = hipMalloc(&h->d_vt, sizeof(HvpTables));
+    if (e == hipSuccess) e = hipnlp_internal_memcpy(h->d_vt, t, sizeof(HvpTables), hipMemcpyHostToDevice);
+    delete t;
+    if (e != hipSuccess) {
+        if (h->d_vt) (void)hipFree(h->d_vt);
+        h->d_vt = nullptr;
+        h->err = std::string("Hessian-vector tables: ") + hipGetErrorString(e);
+        return HIPNLP_E_NODEVICE;
+    }
+    return HIPNLP_OK;
+}
+int hipnlp_eval_hess_vec_device(hipnlp_handle* h, const double* x_dev, const double* obj_factor_dev, const double* lambda_dev, const double* v_dev, double* out_dev, void* stream) {
+    if (!h || !x_dev || !obj_factor_dev || !lambda_dev || !v_dev || !out_dev) return HIPNLP_E_INVALID;
+    NOT_FRONT(h, "hipnlp_eval_hess_vec_device");
+    if (h->kb != 0 || h->ke != h->L.N) {
+        h->err = "hipnlp_eval_hess_vec_device: a shard handle (knot_begin / knot_end not the whole horizon) — the periodicity coupling needs both horizon ends";
+        return HIPNLP_E_UNSUPPORTED;
+    }
+    if (!h->params_set) { h->err = "parameters not set (hipnlp_set_params)"; return HIPNLP_E_PARAMS; }
+    const int rc = hvp_prepare(h, "hipnlp_eval_hess_vec_device");
+    if (rc != HIPNLP_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->dev));
+    hipStream_t s = stream ? hipStream_t(stream) : h->stream;
+    if (h->hseq == INT32_MAX) {   // (generation of the Hessian kernels' non-finite flags: start over before it wraps, as hess_launch does)
+        HIP_TRY(h, hipDeviceSynchronize());
+        HIP_TRY(h, hipMemset(h->d_hflag, 0, size_t(h->batch) * sizeof(int32_t)));
+        std::memset(h->h_hflag, 0, size_t(h->batch) * sizeof(int32_t));
+        HIP_TRY(h, hipDeviceSynchronize());
+        h->hseq = 0;
+    }
+    VArgs a;
+    a.tb = h->d_tb; a.ht = h->d_ht; a.vt = h->d_vt; a.x = x_dev; a.pk = h->d_pk; a.gp = h->d_gp;
+    a.sigma = obj_factor_dev; a.lambda = lambda_dev; a.v = v_dev; a.out = out_dev; a.flag = h->d_hflag;
+    a.N = h->L.N; a.n = h->L.n; a.m = h->L.m; a.seq = ++h->hseq; a.n_couple = h->HL.n_couple;
+    const dim3 grid(unsigned(h->nk), unsigned(h->batch));
+    if (h->d.settings.terrain == HIPNLP_TERRAIN_PLANAR) hipLaunchKernelGGL(hipnlp_knot_hvp_kernel<HIPNLP_TERRAIN_PLANAR>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(hipnlp_knot_hvp_kernel<HIPNLP_TERRAIN_SMOOTH_STEPS>, grid, dim3(256), 0, s, a);
+    HIP_TRY(h, hipGetLastError());
+    return HIPNLP_OK;
+}
+int hipnlp_hess_times_device(hipnlp_handle* h, const double* values_dev, const double* v_dev, double* out_dev, void* stream) {
+    if (!h || !values_dev || !v_dev || !out_dev) return HIPNLP_E_INVALID;
+    NOT_FRONT(h, "hipnlp_hess_times_device");
+    if (h->kb != 0 || h->ke != h->L.N) {
+        h->err = "hipnlp_hess_times_device: a shard handle (knot_begin / knot_end not the whole horizon) — the periodicity coupling needs both horizon ends";
+        return HIPNLP_E_UNSUPPORTED;
+    }
+    const int rc = hvp_prepare(h, "hipnlp_hess_times_device");
+    if (rc != HIPNLP_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->dev));
+    TArgs a;
+    a.vt = h->d_vt; a.values = values_dev; a.v = v_dev; a.out = out_dev;
+    a.N = h->L.N; a.n = h->L.n; a.nnz_knot = h->HL.nnz_knot; a.n_couple = h->HL.n_couple; a.nnz_h = hess_count(h);
+    hipLaunchKernelGGL(hipnlp_hess_times_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(256), 0, stream ? hipStream_t(stream) : h->stream, a);
     HIP_TRY(h, hipGetLastError());
     return HIPNLP_OK;
 }

@@ -636,10 +636,13 @@ template <class Em> HD void t_kh_diag_planar(KHCtx<Em>& h, int t) { if (terrain_
 template <class Em> HD void t_kh_diag_smooth(KHCtx<Em>& h, int t) { if (!terrain_is_planar(h.cx)) t_kh_diag(h, t); }
 
 // --- periodicity cost, coupling of the last knot with the first: lanes 84 (last knot only) -------------------------------------
+// the value of every coupling entry (it does not depend on x): ONE expression for the Hessian program and for the Hessian-vector product,
+// whose first knot needs the value the last knot emits (hipnlp.hip hipnlp_knot_hvp_kernel) — the bits agree
+HD double kh_percouple_value(double sigma, double periodicity_weight) { return -2.0 * sigma * periodicity_weight; }
 template <class Em> HD void t_kh_percouple(KHCtx<Em>& h, int i) {
     Ctx<Em>& cx = h.cx;
     if (cx.st.periodicity_type != HIPNLP_EXPR_MINIMIZE || !cx.ki.last) return;
-    cx.em.H(hk::PERC + i, int(end_tables(cx).per_var[i]), COL_FIRST + int(end_tables(cx).per_var[i]), -2.0 * h.hx.sigma * cx.st.periodicity_weight);
+    cx.em.H(hk::PERC + i, int(end_tables(cx).per_var[i]), COL_FIRST + int(end_tables(cx).per_var[i]), kh_percouple_value(h.hx.sigma, cx.st.periodicity_weight));
 }
 
 // --- centroidal momentum, shared quantities: lane 0 ---------------------------------------------------------------------------------

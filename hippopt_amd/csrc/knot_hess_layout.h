@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "knot_hess_body.h"
+#include "knot_hvp.h"
 #include "layout.h"
 
 namespace hipnlp {
@@ -27,6 +28,14 @@ struct HessLayout {
     // block — the point columns come first in (column, row) order — that are ALL final behind barrier number EARLY_PHASE
     std::vector<unsigned char> pos_phase;
     int early_run = 0, early_phase = 0;   // early_phase: the barrier (1 = the first) behind which the run is final — the earliest of the first three that gives the longest run
+    // Hessian-vector product (knot_hvp.h): hv_touch[hv_beg[i] .. hv_beg[i + 1]) the touches of variable i of a knot record — the entries of
+    // the block that have i as row or as column, in block-position order, a diagonal entry once; hv_K[i] their number; hv_couple[i] the
+    // coupling entry of variable i (the same variable at both horizon ends) or -1.  hvp_ok: the tables fit the device kernels' staging
+    // (else hvp_error).
+    std::vector<HvpTouch> hv_touch;
+    std::vector<int32_t> hv_beg, hv_K, hv_couple;
+    bool hvp_ok = false;
+    std::string hvp_error;
     std::string error;
 
     bool build(const hipnlp_settings& st, const KinTables& kt) {
@@ -85,7 +94,41 @@ struct HessLayout {
         nnz_knot = int(perm.size());
         n_couple = int(perm_couple.size());
         nnz = long(nnz_knot) * N + n_couple;
+        build_hvp();
         return true;
+    }
+    void build_hvp() {
+        std::vector<std::vector<HvpTouch>> per(NXK);
+        hvp_ok = true;
+        hvp_error.clear();
+        for (int p = 0; p < nnz_knot && hvp_ok; ++p) {
+            const int r = lrow[size_t(p)], c = lcol[size_t(p)];
+            if (r < 0 || r >= NXK || c < 0 || c >= NXK) { hvp_ok = false; hvp_error = "a Hessian entry outside the knot record (a horizon-global variable)"; break; }
+            per[size_t(r)].push_back({p, perm[size_t(p)], c});
+            if (c != r) per[size_t(c)].push_back({p, perm[size_t(p)], r});
+        }
+        hv_touch.clear();
+        hv_beg.assign(NXK + 1, 0);
+        hv_K.assign(NXK, 0);
+        hv_couple.assign(NXK, -1);
+        if (!hvp_ok) return;
+        for (int i = 0; i < NXK; ++i) {
+            hv_K[size_t(i)] = int32_t(per[size_t(i)].size());
+            hv_touch.insert(hv_touch.end(), per[size_t(i)].begin(), per[size_t(i)].end());
+            hv_beg[size_t(i) + 1] = int32_t(hv_touch.size());
+        }
+        for (int i = 0; i < n_couple; ++i) {
+            const int r = crow[size_t(i)];
+            if (r != ccol[size_t(i)] || r < 0 || r >= NXK || hv_couple[size_t(r)] >= 0) { hvp_ok = false; hvp_error = "a periodicity coupling entry that does not pair a variable with itself"; return; }
+            hv_couple[size_t(r)] = i;
+        }
+        int kmax = 0;
+        for (int i = 0; i < NXK; ++i) kmax = std::max(kmax, int(hv_K[size_t(i)]));
+        if (int(hv_touch.size()) > HVP_WORD_CAP || kmax >= (1 << HVP_CNT_BITS) || hk::COUNT > (1 << HVP_IDX_BITS)) {
+            hvp_ok = false;
+            hvp_error = "a knot block of the Hessian has " + std::to_string(hv_touch.size()) + " touches, at most " + std::to_string(kmax) +
+                        " per variable: more than the Hessian-vector kernels stage (" + std::to_string(HVP_WORD_CAP) + " / " + std::to_string((1 << HVP_CNT_BITS) - 1) + ")";
+        }
     }
     long knot_base(int k) const { return long(nnz_knot) * k; }
     long couple_base() const { return long(nnz_knot) * N; }

@@ -27,7 +27,7 @@ EXPORTS = [
     "hipnlp_ipc_alloc", "hipnlp_ipc_open", "hipnlp_ipc_close", "hipnlp_ipc_free", "hipnlp_peer_push", "hipnlp_peer_signal", "hipnlp_peer_signal_checked", "hipnlp_peer_wait", "hipnlp_eval_device_peers",
     "hipnlp_device_numa_node", "hipnlp_pin_thread_to_device_numa_node",
     "hipnlp_hess_nnz", "hipnlp_hess_sparsity", "hipnlp_eval_hess", "hipnlp_eval_hess_at", "hipnlp_set_hessian_early_run", "hipnlp_get_hessian_early_run", "hipnlp_hessian_early_run_reason", "hipnlp_eval_hess_device",
-    "hipnlp_eval_lagrangian_grad_device",
+    "hipnlp_eval_lagrangian_grad_device", "hipnlp_eval_hess_vec_device", "hipnlp_hess_times_device",
     "hipnlp_eval_pinned", "hipnlp_set_prefetch", "hipnlp_set_early_outputs", "hipnlp_set_host_timing", "hipnlp_host_register", "hipnlp_host_unregister",
     "hipnlp_multi_create", "hipnlp_multi_plan", "hipnlp_multi_info", "hipnlp_multi_breakdown", "hipnlp_multi_set_threads",
     "hipnlp_host_breakdown", "hipnlp_set_auto_register", "hipnlp_host_stats", "hipnlp_set_constant_jacobian", "hipnlp_forget_jac_destination", "hipnlp_jac_constant_mask", "hipnlp_host_release_auto_ranges",
@@ -208,6 +208,9 @@ def load_library(path=None):
     lib.hipnlp_multi_set_threads.argtypes = [vp, C.c_int, C.c_double]
     if hasattr(lib, "hipnlp_eval_lagrangian_grad_device"):   # (builds of earlier versions, loaded by path for comparisons, do not have it)
         lib.hipnlp_eval_lagrangian_grad_device.argtypes = [vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "hipnlp_eval_hess_vec_device"):
+        lib.hipnlp_eval_hess_vec_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        lib.hipnlp_hess_times_device.argtypes = [vp, vp, vp, vp, vp]
     _libs[path] = lib
     return lib
 
@@ -576,6 +579,18 @@ class HipNlp:
         tensor.data_ptr()) of x [batch][n], obj_factor [batch], lam [batch][m]; one launch, asynchronous on `stream`"""
         vp = C.c_void_p
         self._check(self.lib.hipnlp_eval_lagrangian_grad_device(self.h, vp(x_ptr), vp(obj_factor_ptr), vp(lam_ptr), vp(out_ptr), vp(stream or None)))
+
+    def eval_hess_vec_device(self, x_ptr, obj_factor_ptr, lam_ptr, v_ptr, out_ptr, stream=0):
+        """out [batch][n] = H(x, obj_factor, lam) v (hipnlp_eval_hess_vec_device): device pointers of x, v [batch][n], obj_factor
+        [batch], lam [batch][m]; one launch, H is never written, asynchronous on `stream`; out may not alias v or x"""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_eval_hess_vec_device(self.h, vp(x_ptr), vp(obj_factor_ptr), vp(lam_ptr), vp(v_ptr), vp(out_ptr), vp(stream or None)))
+
+    def hess_times_device(self, values_ptr, v_ptr, out_ptr, stream=0):
+        """out [batch][n] = H v from the values [batch][nnz_h] eval_hess_device of this handle wrote (hipnlp_hess_times_device): bit for
+        bit the result of eval_hess_vec_device; asynchronous on `stream`; out may not alias v"""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_hess_times_device(self.h, vp(values_ptr), vp(v_ptr), vp(out_ptr), vp(stream or None)))
 
     def cost_terms(self):
         out = np.empty((self.batch, _abi.NCOST_TERMS))

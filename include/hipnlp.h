@@ -432,6 +432,26 @@ int hipnlp_eval_device(hipnlp_handle* h, const double* x_dev,
 int hipnlp_eval_lagrangian_grad_device(hipnlp_handle* h, const double* x_dev, const double* obj_factor_dev, const double* lambda_dev,
                                        double* out_dev, void* stream);
 
+/* Hessian of the Lagrangian times a vector  out = H(x, obj_factor, lambda) v,  per trajectory: the second-order object a device-side
+ * consumer needs (a Newton-CG or truncated-Newton step, a gradient penalty, a Lanczos estimate of curvature, the double backward of
+ * hippopt_amd.autograd).  Shapes and stream rules of hipnlp_eval_hess_device: x_dev, v_dev, out_dev [batch][n], obj_factor_dev [batch],
+ * lambda_dev [batch][m] (m of THIS handle: the reduced rows of a HIPNLP_FLAG_DETECT_SIMPLE_BOUNDS handle); device pointers, enqueued on
+ * `stream` (NULL = the handle's own), not synchronised.  ONE launch, H is never written: the Hessian is block diagonal by knot, every
+ * knot's workgroup runs the Hessian program and sums its 189 variables over the entries it holds in LDS — 189 doubles
+ * leave per knot instead of 1 539 / 1 878; the six horizon-global elements of out are zero.  Every element of out is written exactly once.
+ * Each variable is summed in a fixed order (knot_hvp.h): the same bits at every position of a batch, for every jac order, and as
+ * hipnlp_hess_times_device on the values of hipnlp_eval_hess_device.  out_dev may NOT alias v_dev or x_dev (other knots' workgroups read
+ * them).  A NaN / Inf in the result raises the handle's Hessian non-finite flag, as hipnlp_eval_hess_device does.
+ * Returns HIPNLP_E_PARAMS before hipnlp_set_params; HIPNLP_E_UNSUPPORTED on a multi-device handle and on a shard handle (knot_begin /
+ * knot_end not the whole horizon: the periodicity coupling needs both horizon ends), hipnlp_last_error says which. */
+int hipnlp_eval_hess_vec_device(hipnlp_handle* h, const double* x_dev, const double* obj_factor_dev, const double* lambda_dev,
+                                const double* v_dev, double* out_dev, void* stream);
+/* out = H v from a value run values_dev [batch][nnz_h] that hipnlp_eval_hess_device of the SAME handle wrote: for many products at one x
+ * (the inner iterations of a CG solve).  No x, no parameters, no multipliers; v_dev, out_dev [batch][n], out_dev may not alias v_dev;
+ * stream rules and error codes as above (no HIPNLP_E_PARAMS).  Order and arithmetic are those of hipnlp_eval_hess_vec_device: bit for
+ * bit its result. */
+int hipnlp_hess_times_device(hipnlp_handle* h, const double* values_dev, const double* v_dev, double* out_dev, void* stream);
+
 /* Sharded variant (multi-GPU): the handle owns knots [knot_begin, knot_end).  Outputs are
  * shard-local and contiguous so that one RCCL all-gather reassembles them:
  *   grad_shard [batch][shard_grad]  = grad f entries of the shard's knots (+ the 6 global entries on the last shard)
