@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "knot_hess_layout.h"
+#include "knot_stage.h"
 #include "layout.h"
 
 using namespace hipnlp;
@@ -202,12 +203,6 @@ template <> struct alignas(16) SharedTablesT<true> {   // without the blocks rea
 using SharedTables = SharedTablesT<false>;
 static_assert(sizeof(KSettings) % 8 == 0 && sizeof(KinLite) % 8 == 0 && sizeof(GParamsLite) % 8 == 0, "copied in 8-byte words");
 
-// Workgroup barrier that orders LDS traffic only.  The phases of the knot program exchange data through LDS and through nothing
-// else, so global loads may stay in flight across it: __syncthreads() carries a workgroup fence whose s_waitcnt vmcnt(0) makes every
-// barrier wait for the copy-out tables prefetched at the top of the kernel.  (The "memory" clobber keeps the compiler from moving
-// memory operations across it; the hardware wait covers the LDS operations of this wave.)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // Tag of a published cost partial (eight-wave variant): the pair {v, v ^ pub_pattern(seq)} is valid for launch `seq` and for no other,
 // whichever of its two words a reader happens to see first (see the reducer in hipnlp_knot_kernel).
 __device__ __forceinline__ unsigned long long pub_pattern(int32_t seq) { return ((unsigned long long)(uint32_t)seq * 0x9E3779B97F4A7C15ull) | 1ull; }
@@ -310,12 +305,6 @@ void hipnlp_knot_kernel(const DeviceTables* tb_p, const double* x_p, const doubl
     unsigned long long st_issued = 0, st_loaded = 0;
 #endif
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    // workgroup -> knot, XCD-aware: workgroups are dealt round-robin over the 8 XCDs (observed, relied on for speed only), each with
-    // its own L2, so within one trajectory (one grid row) the workgroups x, x + 8, x + 16, ... share an XCD: they get CONSECUTIVE
-    // knots.  The neighbour record x_{k-1} every knot reads is then found in the L2 its owner just filled, and the short runs that
-    // neighbouring knots write into one 128-byte line of a constraint block of g meet in one L2 before they leave for HBM
-    // (measured, 100 knots x 64, HBM bytes per launch: 26.6 -> 16.5 MB read, 109.6 -> 96.1 MB written; algorithmic: 13.7 + 94.7 MB).
-    // A bijection for any row length: class j = x mod 8 owns q + (j < r) knots, q = nk / 8, r = nk mod 8.
     const int b = blockIdx.y;
     // (launches of at most 256 knots per trajectory: one more workgroup per grid row, the trajectory's cost reducer)
     const unsigned nkx = unsigned(nk_p);   // (= gridDim.x, less the reducer; preloaded: the grid size is a kernarg load away)
@@ -412,18 +401,13 @@ void hipnlp_knot_kernel(const DeviceTables* tb_p, const double* x_p, const doubl
     }
     const bool wg_m = SPLIT && blockIdx.x >= nkx;              // (SPLIT) this workgroup runs the model-free half of the knot program
     const unsigned bx = wg_m ? blockIdx.x - nkx : blockIdx.x;  // (both halves of a knot walk the XCDs the same way: they read the same records)
-    const int kk = int((bx & 7u) * (nkx >> 3) + min(bx & 7u, nkx & 7u) + (bx >> 3));
+    const int kk = xcd_knot(bx, nkx);
     const int k = kb_p + kk;
     const int N = N_p;
     const double* x = x_p + size_t(b) * n_p;
     const int first = k == 0, last = k == N - 1;
     const DeviceTables& tb = *tb_p;
-    // ---- stage the knot records and the tables in LDS: straight from global memory into LDS (global_load_lds_dwordx4: lane l of a wave
-    // delivers 16 bytes at LDS base + 16 l — no VGPR round trip, no ds_write; one instruction moves 1 KB), the 1 KB chunks of all
-    // blocks dealt round-robin over the waves.  (The previous version — every thread loads 8-byte words into registers and stores them
-    // to LDS — spent ~250 instructions per wave here, a tenth of the 100-knot launch.)
-    // Full layout: the whole HeadTables + GParams.  Compact layout: KSettings, the KinLite prefix of the kinematic tables and the
-    // GParamsLite prefix of the parameters.
+    // ---- stage the knot records and the tables in LDS (knot_stage.h, KnotStage).
     // Copy-out tables of this knot's variant: fetched once the staging loads have landed (the compiler waits for EVERY outstanding
     // load before an LDS access that follows a direct load), consumed at the very end — they stay in flight across the (LDS-only)
     // barriers of the program.
@@ -471,56 +455,11 @@ void hipnlp_knot_kernel(const DeviceTables* tb_p, const double* x_p, const doubl
         asm volatile("" : "+v"(jpg));
     };
     {
-        static_assert(sizeof(KSettings) % 16 == 0 && sizeof(KinLite) % 16 == 0 && sizeof(GParamsLite) % 16 == 0 && sizeof(HeadTables) % 16 == 0 &&
-                      sizeof(GParams) % 16 == 0 && (PK_STRIDE * 8) % 16 == 0, "staged in 16-byte pieces");
-        // the record x_k is NXK = 189 doubles: 94 pieces + one double, which goes through a register like the gathered words below
-        constexpr int XB = NXK * 8 / 16 * 16, XREM = NXK - XB / 8;
-        static_assert(XREM <= 1 && NXG * 8 % 16 == 0 && NXG <= 8, "record staging");
-        // (scalars of the copy-out, used at the end: read BEFORE the direct loads — behind them the compiler no longer treats global
-        //  memory as unwritten and would fetch these through vector registers)
+        // (scalars of the copy-out, used at the end: read BEFORE the direct loads, see KnotStage)
         nnz_first = tb.nnz_v[VAR_FIRST]; nnz_interior = tb.nnz_v[VAR_INTERIOR]; jac_glob_base = tb.jac_glob_base;
         n_glob = tb.n_glob;
-        const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-        // a block of `bytes` (multiple of 16): wave (w + rot) mod WAVES moves the 1 KB chunk w of each round of WG x 16 bytes; `rot`
-        // walks on by the chunks used, so that the small blocks land on different waves (everything here folds at compile time
-        // except the wave number: no scalar branch, one predicated instruction per block and round)
-        int rot = 0;
-        auto stage = [&](const void* src, void* dst, int bytes) __attribute__((always_inline)) {
-            for (int r0 = 0; r0 < bytes; r0 += WG * 16) {
-                const int wv = (wave_u + WAVES - rot % WAVES) & (WAVES - 1);
-                const int off = r0 + wv * 1024 + lane * 16;
-                if (off < bytes)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(static_cast<const char*>(src) + off),
-                                                     (__attribute__((address_space(3))) void*)(static_cast<char*>(dst) + r0 + wv * 1024), 16, 0, 0);
-                rot += ((bytes - r0 < WG * 16 ? bytes - r0 : WG * 16) + 1023) / 1024;
-            }
-        };
-        stage(x + size_t(NXK) * k, s.x, XB);
-        if (!first) stage(x + size_t(NXK) * (k - 1), s.xm, XB); else rot += (XB + 1023) / 1024;
-        stage(pk_p + (size_t(b) * N + k) * PK_STRIDE, s.pk, PK_STRIDE * 8);
-        stage(x + size_t(NXK) * N, s.xg, NXG * 8);
-        if constexpr (COMPACT) {
-            stage(static_cast<const GParamsLite*>(gp_p + b), &tabs.gp, int(sizeof(GParamsLite)));
-            stage(&tb.head.ks, &tabs.ks, int(sizeof(KSettings)));
-            stage(static_cast<const KinLite*>(&tb.head.kt), &tabs.kt, int(sizeof(KinLite)));
-        } else {
-#ifdef HIPNLP_DIAG_LITE_STAGE
-            // timing-only diagnostic build (wrong values): the eight-wave kernel stages the lite tables only — 10.6 instead of 26.4 KB per
-            // workgroup: what a shorter prologue could be worth on the 100-knot launch
-            stage(static_cast<const GParamsLite*>(gp_p + b), &tabs.gp, int(sizeof(GParamsLite)));
-            stage(static_cast<const KinLite*>(&tb.head.kt), &tabs.head.kt, int(sizeof(KinLite)));
-            stage(&tb.head.ks, &tabs.head.ks, int(sizeof(KSettings)));
-#else
-            stage(gp_p + b, &tabs.gp, int(sizeof(GParams)));
-            // (SPLIT: both halves stage every table.  The model-free half without the joint frames and link inertials it never reads — 5.2 of the
-            //  8.4 KB — measured no different: 7.47 - 7.54 against 7.46 - 7.48 us per 100-knot launch)
-            stage(&tb.head, &tabs.head, int(sizeof(HeadTables)));
-#endif
-        }
-        // through registers: the odd last double of the two records; horizon ends only: the periodicity variables of the other end
-        double xrem = 0.0, xov = 0.0;
-        if (XREM && tid < 2 && !(first && tid == 1)) xrem = x[size_t(NXK) * (k - tid) + XB / 8];
-        if constexpr (!Scratch::trimmed) { if (first || last) { if (tid < NPER) xov = x[size_t(NXK) * (first ? N - 1 : 0) + periodicity_row_var(tid)]; } }
+        KnotStage<WAVES> st(tid);
+        st.template issue<COMPACT>(s, tabs, tb, x, pk_p, gp_p, b, k, N);
 #ifdef HIPNLP_STAMPS
         st_issued = __builtin_amdgcn_s_memtime();
 #endif
@@ -531,12 +470,7 @@ void hipnlp_knot_kernel(const DeviceTables* tb_p, const double* x_p, const doubl
 #ifdef HIPNLP_STAMPS
         st_loaded = __builtin_amdgcn_s_memtime();
 #endif
-        if constexpr (!Scratch::trimmed) { if (first || last) { if (tid < NPER) s.xo[tid] = xov; } }
-        if (XREM && tid < 2) (tid ? s.xm : s.x)[XB / 8] = xrem;
-        if (first) { for (int i = tid; i < XB / 8; i += WG) s.xm[i] = 0.0; }
-        // pads (no staging load touches them)
-        if (tid >= 64 && tid < 64 + Scratch::xpad - NXK) { s.x[NXK + tid - 64] = 0.0; s.xm[NXK + tid - 64] = 0.0; }
-        if (tid >= 128 && tid < 128 + 8 - NXG) s.xg[NXG + tid - 128] = 0.0;
+        st.land(s);
         // copy-out tables: issued now, consumed at the very end (LATE_TABLES: issued behind the last barrier but one instead — the
         // registers they occupy from here to the end are what stands between the four-wave VARY kernel and a fifth wave per SIMD)
         if constexpr (!LATE_TABLES && !TABLES_WITH_STAGING) fetch_tables();
@@ -572,11 +506,7 @@ void hipnlp_knot_kernel(const DeviceTables* tb_p, const double* x_p, const doubl
     Ctx<Em> cx(s, tabs.kin(), tabs.settings(), tabs.gp, ki, em, COMPACT ? &tb.head.kt : nullptr, COMPACT ? gp_p + b : nullptr);
     if constexpr (Scratch::trimmed) cx.x_other = x + size_t(NXK) * (first ? N - 1 : 0);
     static_assert(!Scratch::hd_on_rw || hdyn_entries_early<Em>, "hd on Rw[1..]: only where the momentum rows are summed in the first phase (KnotScratchT::hd_on_rw)");
-    // The program is instantiated ONCE PER WAVE (a generic lambda over the wave number as a compile-time constant: a task group is
-    // compiled into the one instance whose wave runs it) and dispatched by one switch, so that every wave executes a CONTIGUOUS
-    // instruction stream from the first phase to the last.  Written as `if (wave == w) { ... }` blocks phase after phase, every
-    // wave jumped over the other waves' code several times per phase, each jump a cold instruction-cache line.  The waves still meet
-    // at the same barriers: every instance contains all of them.
+    // (one contiguous program instance per wave: knot_stage.h, dispatch_wave)
 #define HIPNLP_W8(p, s) (TERRAIN == HIPNLP_TERRAIN_PLANAR ? (p) : (s))
 #define HIPNLP_W4(p, s) (TERRAIN == HIPNLP_TERRAIN_PLANAR ? (p) : (s))
 #ifdef HIPNLP_STAMPS
@@ -657,19 +587,7 @@ void hipnlp_knot_kernel(const DeviceTables* tb_p, const double* x_p, const doubl
     for (int pass_ = 0; pass_ < 2; ++pass_) {
     if (pass_ == 1) { for (int i = 0; i < 8; ++i) st_first[i] = st_arr[i]; st_first0 = st_staged; bid = 0; st_nt = 0; __syncthreads(); st_first[7] = __builtin_amdgcn_s_memtime(); }
 #endif
-    // (on the wave number as a SCALAR: dispatched on the per-lane value the switch is built out of execution masks — every instance skipped
-    //  by a branch on an empty mask — and the path that skips them all reaches the copy-out with the table fetch unconsumed: the wait that
-    //  tables_are_here() moves in front of the early stores would be back in front of the final ones)
-    switch (__builtin_amdgcn_readfirstlane(wave)) {
-        case 0: run_wave(std::integral_constant<int, 0>{}); break;
-        case 1: run_wave(std::integral_constant<int, 1>{}); break;
-        case 2: run_wave(std::integral_constant<int, 2>{}); break;
-        case 3: run_wave(std::integral_constant<int, 3>{}); break;
-        case 4: if constexpr (WAVES == 8) run_wave(std::integral_constant<int, 4>{}); break;
-        case 5: if constexpr (WAVES == 8) run_wave(std::integral_constant<int, 5>{}); break;
-        case 6: if constexpr (WAVES == 8) run_wave(std::integral_constant<int, 6>{}); break;
-        default: if constexpr (WAVES == 8) run_wave(std::integral_constant<int, 7>{}); break;
-    }
+    dispatch_wave<WAVES>(wave, run_wave);
 #ifdef HIPNLP_TWOPASS
     }
 #endif
@@ -887,10 +805,7 @@ void hipnlp_knot_hess_kernel(HArgs a) {
     using Em = DevEmH<TERRAIN, LAYOUT, DIRECT>;
     using Scratch = typename Em::Scratch;
     constexpr bool COMPACT = Scratch::compact;
-    static_assert(offsetof(Scratch, jac) + sizeof(Scratch::jac) + 16 > sizeof(Scratch) && offsetof(Scratch, grad) + sizeof(Scratch::grad) == offsetof(Scratch, jac),
-                  "grad and jac are the last members of the scratch (up to tail padding)");
-    constexpr size_t S_BYTES = offsetof(Scratch, grad);
-    static_assert(S_BYTES % 16 == 0, "scratch prefix");
+    constexpr size_t S_BYTES = HessScratchPrefix<Scratch>::BYTES;   // (without grad and jac: knot_stage.h)
     constexpr int WG = 256;
     __shared__ alignas(16) double s_raw[S_BYTES / sizeof(double)];
     Scratch& s = *reinterpret_cast<Scratch*>(s_raw);
@@ -907,70 +822,23 @@ void hipnlp_knot_hess_kernel(HArgs a) {
     constexpr int G_USED = COMPACT ? gs::FIN : gs::COUNT;   // multipliers staged by native slot (compact: the horizon-end rows have no storage in g[])
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int b = blockIdx.y;
-    const int kk = int((blockIdx.x & 7u) * (gridDim.x >> 3) + min(blockIdx.x & 7u, gridDim.x & 7u) + (blockIdx.x >> 3));   // (XCD-aware, as in hipnlp_knot_kernel)
+    const int kk = xcd_knot(blockIdx.x, gridDim.x);
     const int k = a.knot_begin + kk, N = a.N;
     const int first = k == 0, last = k == N - 1;
     const double* x = a.x + size_t(b) * a.n;
     const DeviceTables& tb = *a.tb;
     {
-        // staged as in hipnlp_knot_kernel: records and tables straight from global memory into LDS, 1 KB chunks dealt over the waves
-        constexpr int WAVES = WG / 64;
-        constexpr int XB = NXK * 8 / 16 * 16, XREM = NXK - XB / 8;
-        const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-        int rot = 0;
-        auto stage = [&](const void* src, void* dst, int bytes) __attribute__((always_inline)) {
-            for (int r0 = 0; r0 < bytes; r0 += WG * 16) {
-                const int wv = (wave_u + WAVES - rot % WAVES) & (WAVES - 1);
-                const int off = r0 + wv * 1024 + lane * 16;
-                if (off < bytes)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(static_cast<const char*>(src) + off),
-                                                     (__attribute__((address_space(3))) void*)(static_cast<char*>(dst) + r0 + wv * 1024), 16, 0, 0);
-                rot += ((bytes - r0 < WG * 16 ? bytes - r0 : WG * 16) + 1023) / 1024;
-            }
-        };
-        // multipliers of the rows this knot owns, by native slot (the same slot -> row map that scatters g), in the g staging area of
-        // the scratch (the Hessian program emits no g); of the next interval's angular momentum rows.  Two dependent global reads
-        // (row map, then multiplier): all row-map words first, all multipliers behind them — two round trips, not two per iteration.
-        const double* lam = a.lambda + size_t(b) * a.m;
-        const int v = first ? VAR_FIRST : (last ? VAR_LAST : VAR_INTERIOR);
-        constexpr int LG_ITERS = (gs::COUNT + WG - 1) / WG;
-        int lga[LG_ITERS], lgb[LG_ITERS];
-#pragma unroll
-        for (int it = 0; it < LG_ITERS; ++it) { lga[it] = tb.g_a[v][tid + it * WG]; lgb[it] = tb.g_b[tid + it * WG]; }   // (padded tables)
-        int nga = G_NONE, ngb = 0;
-        if (tid < 3 && k + 1 < N) { const int slot = gs::HDYN + 3 + tid; nga = tb.g_a[k + 1 == N - 1 ? VAR_LAST : VAR_INTERIOR][slot]; ngb = tb.g_b[slot]; }
-        const double sig = a.sigma[b];
-        stage(x + size_t(NXK) * k, s.x, XB);
-        if (!first) stage(x + size_t(NXK) * (k - 1), s.xm, XB); else rot += (XB + 1023) / 1024;
-        stage(a.pk + (size_t(b) * N + k) * PK_STRIDE, s.pk, PK_STRIDE * 8);
-        stage(x + size_t(NXK) * N, s.xg, NXG * 8);
-        if constexpr (COMPACT) {
-            stage(static_cast<const GParamsLite*>(a.gp + b), &tabs.gp, int(sizeof(GParamsLite)));
-            stage(&tb.head.ks, &tabs.ks, int(sizeof(KSettings)));
-            stage(static_cast<const KinLite*>(&tb.head.kt), &tabs.kt, int(sizeof(KinLite)));
-        } else {
-            stage(a.gp + b, &tabs.gp, int(sizeof(GParams)));
-            stage(&tb.head, &tabs.head, int(sizeof(HeadTables)));
-        }
-        stage(&a.ht->far, &hx.far, int(sizeof(KHFarLists)));
-        if constexpr (DIRECT) stage(a.ht->inv, inv_s, int(sizeof(inv_s)));
-        double xrem = 0.0, xov = 0.0;
-        if (XREM && tid < 2 && !(first && tid == 1)) xrem = x[size_t(NXK) * (k - tid) + XB / 8];
-        if (first || last) { if (tid < NPER) xov = x[size_t(NXK) * (first ? N - 1 : 0) + periodicity_row_var(tid)]; }
-        double lv[LG_ITERS];
-#pragma unroll
-        for (int it = 0; it < LG_ITERS; ++it) lv[it] = lga[it] != G_NONE ? lam[lga[it] + lgb[it] * k] : 0.0;
-        const double lnext = nga != G_NONE ? lam[nga + ngb * (k + 1)] : 0.0;
+        // records, tables and multipliers -> LDS (knot_stage.h: KnotStage, MultiplierGather)
+        MultiplierGather<G_USED> mg(tb, a.sigma, b, k, N, tid);
+        KnotStage<WG / 64> st(tid);
+        st.template issue<COMPACT>(s, tabs, tb, x, a.pk, a.gp, b, k, N, [&](auto& stg) __attribute__((always_inline)) {
+            stg.block(&a.ht->far, &hx.far, int(sizeof(KHFarLists)));
+            if constexpr (DIRECT) stg.block(a.ht->inv, inv_s, int(sizeof(inv_s)));
+        });
+        mg.issue(a.lambda + size_t(b) * a.m, k);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the staging loads of THIS wave have landed in LDS
-        if (first || last) { if (tid < NPER) s.xo[tid] = xov; }
-        if (XREM && tid < 2) (tid ? s.xm : s.x)[XB / 8] = xrem;
-        if (first) { for (int i = tid; i < XB / 8; i += WG) s.xm[i] = 0.0; }
-        if (tid >= 64 && tid < 64 + XPAD - NXK) { s.x[NXK + tid - 64] = 0.0; s.xm[NXK + tid - 64] = 0.0; }
-        if (tid >= 128 && tid < 128 + 8 - NXG) s.xg[NXG + tid - 128] = 0.0;
-#pragma unroll
-        for (int it = 0; it < LG_ITERS; ++it) { const int slot = tid + it * WG; if (slot < G_USED) s.g[slot] = lv[it]; }
-        if (tid < 3) hx.lam_next[tid] = lnext;
-        if (tid == 0) hx.sigma = sig;
+        st.land(s);
+        mg.store(s, hx);
     }
     lds_barrier();
     // copy-out permutation.  Compact layout (the batch launches, at their register caps): fetched behind the fifth barrier, so that its
@@ -1020,7 +888,7 @@ void hipnlp_knot_hess_kernel(HArgs a) {
 #pragma unroll
             for (int it = 0; it < EARLY_ITERS; ++it) {
                 const int pos = tid + it * WG;
-                // (a store the compiler does not know about, as in hipnlp_knot_kernel: nothing waits for it)
+                // (a store the compiler does not know about, see store_unwaited in hipnlp_knot_kernel: nothing waits for it)
                 if (pos < early_run) asm volatile("global_store_dwordx2 %0, %1, %2 sc0 sc1" ::"v"(pos * 8), "v"(hx.H[hp[it]]), "s"(out) : "memory");
             }
         }
@@ -1029,7 +897,6 @@ void hipnlp_knot_hess_kernel(HArgs a) {
     Em em{s.g, s.jac, DIRECT ? a.hess + int64_t(b) * a.hstride + (int64_t(a.nnz_knot) * k - a.hoff) : hx.H, inv_s, DIRECT ? a.trash + (size_t(blockIdx.y) * gridDim.x + blockIdx.x) : nullptr};
     Ctx<Em> cx(s, tabs.kin(), tabs.settings(), tabs.gp, ki, em, COMPACT ? &tb.head.kt : nullptr, COMPACT ? a.gp + b : nullptr);
     KHCtx<Em> hcx{cx, hx, s.g};
-    // (one contiguous program instance per wave, as in hipnlp_knot_kernel)
 #ifdef HIPNLP_STAMPS
     unsigned long long st_task[24], st_arr[8], st_dep[8];   // diagnostic build: end of every task group of this wave in program order; barrier arrival / departure
     int st_nt = 0, bid = 0;
@@ -1046,15 +913,7 @@ void hipnlp_knot_hess_kernel(HArgs a) {
         constexpr int W = decltype(wc)::value;
         HIPNLP_KNOT_HESS_PROGRAM(DEV_KIN, DEV_RH, DEV_BARRIER)
     };
-    // (dispatched on the wave number as a SCALAR: on the per-lane value the compiler builds the switch out of execution masks — every
-    //  instance skipped by a branch on an empty mask — and a path that skips all four reaches the copy-out with the table fetch unconsumed:
-    //  the wait tables_are_here() moves forward would be back in front of the final stores)
-    switch (__builtin_amdgcn_readfirstlane(wave)) {
-        case 0: run_wave(std::integral_constant<int, 0>{}); break;
-        case 1: run_wave(std::integral_constant<int, 1>{}); break;
-        case 2: run_wave(std::integral_constant<int, 2>{}); break;
-        default: run_wave(std::integral_constant<int, 3>{}); break;
-    }
+    dispatch_wave<4>(wave, run_wave);   // (one contiguous program instance per wave: knot_stage.h)
 #undef DEV_KIN
 #undef DEV_RH
 #undef DEV_BARRIER
@@ -1131,10 +990,7 @@ void hipnlp_knot_hvp_kernel(VArgs a) {
     using Em = DevEmH<TERRAIN, LAYOUT_COMPACT, false>;   // (the staged compact Hessian kernel's emitter: the same program, the same bits of H)
     using Scratch = typename Em::Scratch;
     static_assert(Scratch::compact, "the compact scratch of the batch Hessian kernel");
-    static_assert(offsetof(Scratch, jac) + sizeof(Scratch::jac) + 16 > sizeof(Scratch) && offsetof(Scratch, grad) + sizeof(Scratch::grad) == offsetof(Scratch, jac),
-                  "grad and jac are the last members of the scratch (up to tail padding)");
-    constexpr size_t S_BYTES = offsetof(Scratch, grad);
-    static_assert(S_BYTES % 16 == 0, "scratch prefix");
+    constexpr size_t S_BYTES = HessScratchPrefix<Scratch>::BYTES;   // (without grad and jac: knot_stage.h)
     constexpr int WG = 256;
     __shared__ alignas(16) double s_raw[S_BYTES / sizeof(double)];
     Scratch& s = *reinterpret_cast<Scratch*>(s_raw);
@@ -1150,63 +1006,22 @@ void hipnlp_knot_hvp_kernel(VArgs a) {
     constexpr int G_USED = gs::FIN;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int b = blockIdx.y;
-    const int k = int((blockIdx.x & 7u) * (gridDim.x >> 3) + min(blockIdx.x & 7u, gridDim.x & 7u) + (blockIdx.x >> 3));   // (XCD-aware, as in hipnlp_knot_kernel)
+    const int k = xcd_knot(blockIdx.x, gridDim.x);
     const int N = a.N;
     const int first = k == 0, last = k == N - 1;
     const double* x = a.x + size_t(b) * a.n;
     const DeviceTables& tb = *a.tb;
-    double sig = 0.0;
+    // records, tables and multipliers -> LDS, as hipnlp_knot_hess_kernel<TERRAIN, LAYOUT_COMPACT> (knot_stage.h: KnotStage, MultiplierGather)
+    MultiplierGather<G_USED> mg(tb, a.sigma, b, k, N, tid);
     {
-        // staged as in hipnlp_knot_hess_kernel: records and tables straight from global memory into LDS, 1 KB chunks dealt over the waves
-        constexpr int WAVES = WG / 64;
-        constexpr int XB = NXK * 8 / 16 * 16, XREM = NXK - XB / 8;
-        const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-        int rot = 0;
-        auto stage = [&](const void* src, void* dst, int bytes) __attribute__((always_inline)) {
-            for (int r0 = 0; r0 < bytes; r0 += WG * 16) {
-                const int wv = (wave_u + WAVES - rot % WAVES) & (WAVES - 1);
-                const int off = r0 + wv * 1024 + lane * 16;
-                if (off < bytes)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(static_cast<const char*>(src) + off),
-                                                     (__attribute__((address_space(3))) void*)(static_cast<char*>(dst) + r0 + wv * 1024), 16, 0, 0);
-                rot += ((bytes - r0 < WG * 16 ? bytes - r0 : WG * 16) + 1023) / 1024;
-            }
-        };
-        const double* lam = a.lambda + size_t(b) * a.m;
-        const int v = first ? VAR_FIRST : (last ? VAR_LAST : VAR_INTERIOR);
-        constexpr int LG_ITERS = (gs::COUNT + WG - 1) / WG;
-        int lga[LG_ITERS], lgb[LG_ITERS];
-#pragma unroll
-        for (int it = 0; it < LG_ITERS; ++it) { lga[it] = tb.g_a[v][tid + it * WG]; lgb[it] = tb.g_b[tid + it * WG]; }   // (padded tables)
-        int nga = G_NONE, ngb = 0;
-        if (tid < 3 && k + 1 < N) { const int slot = gs::HDYN + 3 + tid; nga = tb.g_a[k + 1 == N - 1 ? VAR_LAST : VAR_INTERIOR][slot]; ngb = tb.g_b[slot]; }
-        sig = a.sigma[b];
-        stage(x + size_t(NXK) * k, s.x, XB);
-        if (!first) stage(x + size_t(NXK) * (k - 1), s.xm, XB); else rot += (XB + 1023) / 1024;
-        stage(a.pk + (size_t(b) * N + k) * PK_STRIDE, s.pk, PK_STRIDE * 8);
-        stage(x + size_t(NXK) * N, s.xg, NXG * 8);
-        stage(static_cast<const GParamsLite*>(a.gp + b), &tabs.gp, int(sizeof(GParamsLite)));
-        stage(&tb.head.ks, &tabs.ks, int(sizeof(KSettings)));
-        stage(static_cast<const KinLite*>(&tb.head.kt), &tabs.kt, int(sizeof(KinLite)));
-        stage(&a.ht->far, &hx.far, int(sizeof(KHFarLists)));
-        double xrem = 0.0, xov = 0.0;
-        if (XREM && tid < 2 && !(first && tid == 1)) xrem = x[size_t(NXK) * (k - tid) + XB / 8];
-        if (first || last) { if (tid < NPER) xov = x[size_t(NXK) * (first ? N - 1 : 0) + periodicity_row_var(tid)]; }
-        double lv[LG_ITERS];
-#pragma unroll
-        for (int it = 0; it < LG_ITERS; ++it) lv[it] = lga[it] != G_NONE ? lam[lga[it] + lgb[it] * k] : 0.0;
-        const double lnext = nga != G_NONE ? lam[nga + ngb * (k + 1)] : 0.0;
+        KnotStage<WG / 64> st(tid);
+        st.template issue<true>(s, tabs, tb, x, a.pk, a.gp, b, k, N, [&](auto& stg) __attribute__((always_inline)) { stg.block(&a.ht->far, &hx.far, int(sizeof(KHFarLists))); });
+        mg.issue(a.lambda + size_t(b) * a.m, k);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the staging loads of THIS wave have landed in LDS
-        if (first || last) { if (tid < NPER) s.xo[tid] = xov; }
-        if (XREM && tid < 2) (tid ? s.xm : s.x)[XB / 8] = xrem;
-        if (first) { for (int i = tid; i < XB / 8; i += WG) s.xm[i] = 0.0; }
-        if (tid >= 64 && tid < 64 + XPAD - NXK) { s.x[NXK + tid - 64] = 0.0; s.xm[NXK + tid - 64] = 0.0; }
-        if (tid >= 128 && tid < 128 + 8 - NXG) s.xg[NXG + tid - 128] = 0.0;
-#pragma unroll
-        for (int it = 0; it < LG_ITERS; ++it) { const int slot = tid + it * WG; if (slot < G_USED) s.g[slot] = lv[it]; }
-        if (tid < 3) hx.lam_next[tid] = lnext;
-        if (tid == 0) hx.sigma = sig;
+        st.land(s);
+        mg.store(s, hx);
     }
+    const double sig = mg.sig;
     lds_barrier();
     // the touch words, the row word of this thread's variable, its element of v and — first and last knot of a handle with the periodicity
     // as a cost — the same variable of v at the other end of the horizon: fetched behind the fifth barrier, in flight across the last phase
@@ -1237,13 +1052,7 @@ void hipnlp_knot_hvp_kernel(VArgs a) {
         constexpr int W = decltype(wc)::value;
         HIPNLP_KNOT_HESS_PROGRAM(DEV_KIN, DEV_RH, DEV_BARRIER)
     };
-    // (one contiguous program instance per wave, dispatched on the wave number as a scalar, as in hipnlp_knot_hess_kernel)
-    switch (__builtin_amdgcn_readfirstlane(wave)) {
-        case 0: run_wave(std::integral_constant<int, 0>{}); break;
-        case 1: run_wave(std::integral_constant<int, 1>{}); break;
-        case 2: run_wave(std::integral_constant<int, 2>{}); break;
-        default: run_wave(std::integral_constant<int, 3>{}); break;
-    }
+    dispatch_wave<4>(wave, run_wave);   // (one contiguous program instance per wave: knot_stage.h)
 #undef DEV_KIN
 #undef DEV_RH
 #undef DEV_BARRIER
@@ -1367,7 +1176,7 @@ void hipnlp_knot_lgrad_kernel(LArgs a) {
     constexpr int LQ = LG_LAM_CAP / WG, LE = LG_ENT_CAP / WG;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int b = blockIdx.y;
-    const int k = int((blockIdx.x & 7u) * (gridDim.x >> 3) + min(blockIdx.x & 7u, gridDim.x & 7u) + (blockIdx.x >> 3));   // (XCD-aware, as in hipnlp_knot_kernel)
+    const int k = xcd_knot(blockIdx.x, gridDim.x);
     const int N = a.N;
     const int first = k == 0, last = k == N - 1;
     const int v = first ? VAR_FIRST : (last ? VAR_LAST : VAR_INTERIOR);
@@ -1378,40 +1187,14 @@ void hipnlp_knot_lgrad_kernel(LArgs a) {
     int ra[LQ], rb[LQ];
     double sig = 0.0;
     {
-        // staged as in hipnlp_knot_kernel: records and tables straight from global memory into LDS, 1 KB chunks dealt over the waves
-        constexpr int WAVES = WG / 64;
-        constexpr int XB = NXK * 8 / 16 * 16, XREM = NXK - XB / 8;
-        const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-        int rot = 0;
-        auto stage = [&](const void* src, void* dst, int bytes) __attribute__((always_inline)) {
-            for (int r0 = 0; r0 < bytes; r0 += WG * 16) {
-                const int wv = (wave_u + WAVES - rot % WAVES) & (WAVES - 1);
-                const int off = r0 + wv * 1024 + lane * 16;
-                if (off < bytes)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(static_cast<const char*>(src) + off),
-                                                     (__attribute__((address_space(3))) void*)(static_cast<char*>(dst) + r0 + wv * 1024), 16, 0, 0);
-                rot += ((bytes - r0 < WG * 16 ? bytes - r0 : WG * 16) + 1023) / 1024;
-            }
-        };
 #pragma unroll
         for (int it = 0; it < LQ; ++it) { ra[it] = lt.row_a[v][tid + it * WG]; rb[it] = lt.row_b[v][tid + it * WG]; }
         sig = a.sigma[b];
-        stage(x + size_t(NXK) * k, s.x, XB);
-        if (!first) stage(x + size_t(NXK) * (k - 1), s.xm, XB); else rot += (XB + 1023) / 1024;
-        stage(a.pk + (size_t(b) * N + k) * PK_STRIDE, s.pk, PK_STRIDE * 8);
-        stage(x + size_t(NXK) * N, s.xg, NXG * 8);
-        stage(static_cast<const GParamsLite*>(a.gp + b), &tabs.gp, int(sizeof(GParamsLite)));
-        stage(&tb.head.ks, &tabs.ks, int(sizeof(KSettings)));
-        stage(static_cast<const KinLite*>(&tb.head.kt), &tabs.kt, int(sizeof(KinLite)));
-        double xrem = 0.0, xov = 0.0;
-        if (XREM && tid < 2 && !(first && tid == 1)) xrem = x[size_t(NXK) * (k - tid) + XB / 8];
-        if (first || last) { if (tid < NPER) xov = x[size_t(NXK) * (first ? N - 1 : 0) + periodicity_row_var(tid)]; }
+        // records and tables -> LDS, as the four-wave compact hipnlp_knot_kernel (knot_stage.h: KnotStage)
+        KnotStage<WG / 64> st(tid);
+        st.template issue<true>(s, tabs, tb, x, a.pk, a.gp, b, k, N);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the staging loads of THIS wave have landed in LDS
-        if (first || last) { if (tid < NPER) s.xo[tid] = xov; }
-        if (XREM && tid < 2) (tid ? s.xm : s.x)[XB / 8] = xrem;
-        if (first) { for (int i = tid; i < XB / 8; i += WG) s.xm[i] = 0.0; }
-        if (tid >= 64 && tid < 64 + Scratch::xpad - NXK) { s.x[NXK + tid - 64] = 0.0; s.xm[NXK + tid - 64] = 0.0; }
-        if (tid >= 128 && tid < 128 + 8 - NXG) s.xg[NXG + tid - 128] = 0.0;
+        st.land(s);
         // the multipliers: issued now, in flight across the (LDS-only) barriers of the program, staged once it has ended
         const double* lam = a.lambda + size_t(b) * a.m;
 #pragma unroll
@@ -1439,13 +1222,7 @@ void hipnlp_knot_lgrad_kernel(LArgs a) {
         constexpr int W = decltype(wc)::value;
         HIPNLP_KNOT_PROGRAM(DEV_R, DEV_BARRIER)
     };
-    // (one contiguous program instance per wave, dispatched on the wave number as a scalar, as in hipnlp_knot_kernel)
-    switch (__builtin_amdgcn_readfirstlane(wave)) {
-        case 0: run_wave(std::integral_constant<int, 0>{}); break;
-        case 1: run_wave(std::integral_constant<int, 1>{}); break;
-        case 2: run_wave(std::integral_constant<int, 2>{}); break;
-        default: run_wave(std::integral_constant<int, 3>{}); break;
-    }
+    dispatch_wave<4>(wave, run_wave);   // (one contiguous program instance per wave: knot_stage.h)
 #undef DEV_R
 #undef DEV_BARRIER
 #undef HIPNLP_W8
@@ -1758,6 +1535,35 @@ struct hipnlp_handle {
         }                                                                                                                     \
     } while (0)
 
+// The launch number tags the cost partials and is the generation of the non-finite flags: before it would wrap (2^31 launches: hours of
+// back-to-back 100-knot callbacks) everything that carries one starts over.  s: the stream of the launch that is about to be numbered.
+static int restart_generation(hipnlp_handle* h, hipStream_t s) {
+    HIP_TRY(h, hipStreamSynchronize(s));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    HIP_TRY(h, hipMemset(h->d_flag, 0, size_t(h->batch) * sizeof(int32_t)));
+    std::memset(h->h_flag, 0, size_t(h->batch) * sizeof(int32_t));
+    if (h->d_cost_pub) HIP_TRY(h, hipMemset(h->d_cost_pub, 0, 2 * size_t(h->batch) * size_t(h->nk) * NCT * 2 * sizeof(unsigned long long)));
+    HIP_TRY(h, hipDeviceSynchronize());
+    h->seq = 0;
+    h->seq_result = -1;
+    h->have_result = false;
+    return HIPNLP_OK;
+}
+// (the same for hseq, the generation of the Hessian kernels' non-finite flags)
+static int restart_hess_generation(hipnlp_handle* h) {
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, hipMemset(h->d_hflag, 0, size_t(h->batch) * sizeof(int32_t)));
+    std::memset(h->h_hflag, 0, size_t(h->batch) * sizeof(int32_t));
+    HIP_TRY(h, hipDeviceSynchronize());
+    h->hseq = 0;
+    return HIPNLP_OK;
+}
+// entry points that need every knot of the horizon refuse a shard handle; why: what needs them
+static int whole_horizon_only(hipnlp_handle* h, const char* who, const char* why) {
+    if (h->kb == 0 && h->ke == h->L.N) return HIPNLP_OK;
+    h->err = std::string(who) + ": a shard handle (knot_begin / knot_end not the whole horizon) — " + why;
+    return HIPNLP_E_UNSUPPORTED;
+}
 static void free_all(hipnlp_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->dev);
@@ -1784,6 +1590,17 @@ static int drop_stale_range(hipnlp_handle* h, void* p);
 static bool auto_owns(const hipnlp_handle* h, const void* p);
 static double* caller_array_address(hipnlp_handle* h, int q, double* p, size_t bytes);
 static int multi_set_params(hipnlp_handle* h, const double* p);
+// a table built on the host -> device memory of the handle (*dev: null before, and again after a failure)
+static int upload_table(hipnlp_handle* h, void** dev, const void* host, size_t bytes, const char* what) {
+    HIP_TRY(h, hipSetDevice(h->dev));
+    hipError_t e = hipMalloc(dev, bytes);
+    if (e == hipSuccess) e = hipnlp_internal_memcpy(*dev, host, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) return HIPNLP_OK;
+    if (*dev) (void)hipFree(*dev);
+    *dev = nullptr;
+    h->err = std::string(what) + ": " + hipGetErrorString(e);
+    return HIPNLP_E_NODEVICE;
+}
 
 const char* hipnlp_last_error(const hipnlp_handle* h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
@@ -2370,19 +2187,7 @@ static int launch(hipnlp_handle* h, const double* x_dev, double* f_dev, double* 
     // (only launches that store the varying RUN of every block: written through the L2, the early entries of a CCS-ordered block are isolated
     //  doubles on the link — measured 49 -> 258 us per 100-knot call)
     a.early = ((host_block && h->early_store) || h->early_store_always) && vary_only ? 1 : 0;
-    if (h->seq == INT32_MAX) {
-        // the launch number tags the cost partials and is the generation of the non-finite flags: before it would wrap (2^31 launches:
-        // hours of back-to-back 100-knot callbacks) everything that carries one starts over
-        HIP_TRY(h, hipStreamSynchronize(s));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        HIP_TRY(h, hipMemset(h->d_flag, 0, size_t(h->batch) * sizeof(int32_t)));
-        std::memset(h->h_flag, 0, size_t(h->batch) * sizeof(int32_t));
-        if (h->d_cost_pub) HIP_TRY(h, hipMemset(h->d_cost_pub, 0, 2 * size_t(h->batch) * size_t(h->nk) * NCT * 2 * sizeof(unsigned long long)));
-        HIP_TRY(h, hipDeviceSynchronize());
-        h->seq = 0;
-        h->seq_result = -1;
-        h->have_result = false;
-    }
+    if (h->seq == INT32_MAX) { const int rc = restart_generation(h, s); if (rc != HIPNLP_OK) return rc; }
     a.seq = ++h->seq;
     a.cc.parity = cc_parity >= 0 ? (cc_parity & 1) : (a.seq & 1);
     a.N = h->L.N; a.n = h->L.n; a.m = h->L.m; a.nnz = h->L.nnz; a.knot_begin = h->kb; a.nk = h->nk;
@@ -2910,13 +2715,7 @@ static int hess_launch(hipnlp_handle* h, const double* x_dev, const double* sigm
     a.N = h->L.N; a.n = h->L.n; a.m = h->L.m; a.knot_begin = h->kb;
     a.hstride = hess_count(h); a.hoff = h->HL.knot_base(h->kb);
     if (whole_stride > 0) { a.hstride = whole_stride; a.hoff = 0; }
-    if (h->hseq == INT32_MAX) {   // (generation of the Hessian kernel's non-finite flags: start over before it wraps)
-        HIP_TRY(h, hipDeviceSynchronize());
-        HIP_TRY(h, hipMemset(h->d_hflag, 0, size_t(h->batch) * sizeof(int32_t)));
-        std::memset(h->h_hflag, 0, size_t(h->batch) * sizeof(int32_t));
-        HIP_TRY(h, hipDeviceSynchronize());
-        h->hseq = 0;
-    }
+    if (h->hseq == INT32_MAX) { const int rc = restart_hess_generation(h); if (rc != HIPNLP_OK) return rc; }
     a.seq = ++h->hseq; a.nnz_knot = h->HL.nnz_knot;
     a.early_run = (host_block && early && !h->hess_compact && h->HL.early_run <= 3 * 256 && h->HL.early_phase == hess_early_phase(h->d.settings.terrain)) ? h->HL.early_run : 0;
 #ifdef HIPNLP_STAMPS
@@ -2975,41 +2774,21 @@ static int lgrad_prepare(hipnlp_handle* h) {
     if (L.lg_glob.size() > 16) { delete t; h->err = "hipnlp_eval_lagrangian_grad_device: more than 16 entries in the horizon-global columns"; return HIPNLP_E_UNSUPPORTED; }
     for (size_t i = 0; i < L.lg_glob.size(); ++i) t->word[VAR_LAST][LG_ENT_CAP + i] = int32_t(L.lg_glob[i].slot | (L.lg_glob[i].lam << LG_SLOT_BITS));
     for (int c = 0; c < NXG; ++c) { t->beg[VAR_LAST][LG_SPAN_GLOB + c] = LG_ENT_CAP + L.lg_gcbeg[size_t(c)]; t->end[VAR_LAST][LG_SPAN_GLOB + c] = LG_ENT_CAP + L.lg_gcbeg[size_t(c) + 1]; }
-    HIP_TRY(h, hipSetDevice(h->dev));
-    hipError_t e = hipMalloc(&h->d_lt, sizeof(LgradTables));
-    if (e == hipSuccess) e = hipnlp_internal_memcpy(h->d_lt, t, sizeof(LgradTables), hipMemcpyHostToDevice);
+    const int rc = upload_table(h, reinterpret_cast<void**>(&h->d_lt), t, sizeof(LgradTables), "Lagrangian gradient tables");
     delete t;
-    if (e != hipSuccess) {
-        if (h->d_lt) (void)hipFree(h->d_lt);
-        h->d_lt = nullptr;
-        h->err = std::string("Lagrangian gradient tables: ") + hipGetErrorString(e);
-        return HIPNLP_E_NODEVICE;
-    }
-    return HIPNLP_OK;
+    return rc;
 }
 int hipnlp_eval_lagrangian_grad_device(hipnlp_handle* h, const double* x_dev, const double* obj_factor_dev, const double* lambda_dev, double* out_dev, void* stream) {
     if (!h || !x_dev || !obj_factor_dev || !lambda_dev || !out_dev) return HIPNLP_E_INVALID;
     NOT_FRONT(h, "hipnlp_eval_lagrangian_grad_device");
-    if (h->kb != 0 || h->ke != h->L.N) {
-        h->err = "hipnlp_eval_lagrangian_grad_device: a shard handle (knot_begin / knot_end not the whole horizon) — the gradient needs every knot";
-        return HIPNLP_E_UNSUPPORTED;
-    }
+    if (const int rc = whole_horizon_only(h, "hipnlp_eval_lagrangian_grad_device", "the gradient needs every knot")) return rc;
     if (!h->params_set) { h->err = "parameters not set (hipnlp_set_params)"; return HIPNLP_E_PARAMS; }
     const int rc = lgrad_prepare(h);
     if (rc != HIPNLP_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->dev));
     h->have_result = false;
     hipStream_t s = stream ? hipStream_t(stream) : h->stream;
-    if (h->seq == INT32_MAX) {   // (the launch number is the generation of the non-finite flags: start over before it wraps, as launch() does)
-        HIP_TRY(h, hipStreamSynchronize(s));
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        HIP_TRY(h, hipMemset(h->d_flag, 0, size_t(h->batch) * sizeof(int32_t)));
-        std::memset(h->h_flag, 0, size_t(h->batch) * sizeof(int32_t));
-        if (h->d_cost_pub) HIP_TRY(h, hipMemset(h->d_cost_pub, 0, 2 * size_t(h->batch) * size_t(h->nk) * NCT * 2 * sizeof(unsigned long long)));
-        HIP_TRY(h, hipDeviceSynchronize());
-        h->seq = 0;
-        h->seq_result = -1;
-    }
+    if (h->seq == INT32_MAX) { const int rc = restart_generation(h, s); if (rc != HIPNLP_OK) return rc; }
     LArgs a;
     a.tb = h->d_tb; a.lt = h->d_lt; a.x = x_dev; a.pk = h->d_pk; a.gp = h->d_gp;
     a.sigma = obj_factor_dev; a.lambda = lambda_dev; a.out = out_dev; a.flag = h->d_flag;
@@ -3038,37 +2817,20 @@ static int hvp_prepare(hipnlp_handle* h, const char* who) {
         t->couple[i] = HL.hv_couple[size_t(i)];
         t->row[i] = int32_t(HL.hv_beg[size_t(i)] | (HL.hv_K[size_t(i)] << HVP_IDX_BITS) | ((HL.hv_couple[size_t(i)] >= 0 ? 1 : 0) << HVP_COUPLED_BIT));
     }
-    HIP_TRY(h, hipSetDevice(h->dev));
-    hipError_t e = hipMalloc(&h->d_vt, sizeof(HvpTables));
-    if (e == hipSuccess) e = hipnlp_internal_memcpy(h->d_vt, t, sizeof(HvpTables), hipMemcpyHostToDevice);
+    const int rc2 = upload_table(h, reinterpret_cast<void**>(&h->d_vt), t, sizeof(HvpTables), "Hessian-vector tables");
     delete t;
-    if (e != hipSuccess) {
-        if (h->d_vt) (void)hipFree(h->d_vt);
-        h->d_vt = nullptr;
-        h->err = std::string("Hessian-vector tables: ") + hipGetErrorString(e);
-        return HIPNLP_E_NODEVICE;
-    }
-    return HIPNLP_OK;
+    return rc2;
 }
 int hipnlp_eval_hess_vec_device(hipnlp_handle* h, const double* x_dev, const double* obj_factor_dev, const double* lambda_dev, const double* v_dev, double* out_dev, void* stream) {
     if (!h || !x_dev || !obj_factor_dev || !lambda_dev || !v_dev || !out_dev) return HIPNLP_E_INVALID;
     NOT_FRONT(h, "hipnlp_eval_hess_vec_device");
-    if (h->kb != 0 || h->ke != h->L.N) {
-        h->err = "hipnlp_eval_hess_vec_device: a shard handle (knot_begin / knot_end not the whole horizon) — the periodicity coupling needs both horizon ends";
-        return HIPNLP_E_UNSUPPORTED;
-    }
+    if (const int rc = whole_horizon_only(h, "hipnlp_eval_hess_vec_device", "the periodicity coupling needs both horizon ends")) return rc;
     if (!h->params_set) { h->err = "parameters not set (hipnlp_set_params)"; return HIPNLP_E_PARAMS; }
     const int rc = hvp_prepare(h, "hipnlp_eval_hess_vec_device");
     if (rc != HIPNLP_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->dev));
     hipStream_t s = stream ? hipStream_t(stream) : h->stream;
-    if (h->hseq == INT32_MAX) {   // (generation of the Hessian kernels' non-finite flags: start over before it wraps, as hess_launch does)
-        HIP_TRY(h, hipDeviceSynchronize());
-        HIP_TRY(h, hipMemset(h->d_hflag, 0, size_t(h->batch) * sizeof(int32_t)));
-        std::memset(h->h_hflag, 0, size_t(h->batch) * sizeof(int32_t));
-        HIP_TRY(h, hipDeviceSynchronize());
-        h->hseq = 0;
-    }
+    if (h->hseq == INT32_MAX) { const int rc = restart_hess_generation(h); if (rc != HIPNLP_OK) return rc; }
     VArgs a;
     a.tb = h->d_tb; a.ht = h->d_ht; a.vt = h->d_vt; a.x = x_dev; a.pk = h->d_pk; a.gp = h->d_gp;
     a.sigma = obj_factor_dev; a.lambda = lambda_dev; a.v = v_dev; a.out = out_dev; a.flag = h->d_hflag;
@@ -3082,10 +2844,7 @@ int hipnlp_eval_hess_vec_device(hipnlp_handle* h, const double* x_dev, const dou
 int hipnlp_hess_times_device(hipnlp_handle* h, const double* values_dev, const double* v_dev, double* out_dev, void* stream) {
     if (!h || !values_dev || !v_dev || !out_dev) return HIPNLP_E_INVALID;
     NOT_FRONT(h, "hipnlp_hess_times_device");
-    if (h->kb != 0 || h->ke != h->L.N) {
-        h->err = "hipnlp_hess_times_device: a shard handle (knot_begin / knot_end not the whole horizon) — the periodicity coupling needs both horizon ends";
-        return HIPNLP_E_UNSUPPORTED;
-    }
+    if (const int rc = whole_horizon_only(h, "hipnlp_hess_times_device", "the periodicity coupling needs both horizon ends")) return rc;
     const int rc = hvp_prepare(h, "hipnlp_hess_times_device");
     if (rc != HIPNLP_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->dev));

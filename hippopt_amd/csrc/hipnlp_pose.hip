@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "knot_stage.h"
 #include "pose_layout.h"
 
 // (hipnlp.hip: hipMemcpy that survives a host buffer inside a stale self-registered range)
@@ -119,9 +120,6 @@ template <class S, class T> __device__ __forceinline__ PoseHands* pose_hands(S& 
     else return reinterpret_cast<PoseHands*>(s.xo);
 }
 
-// workgroup barrier that orders LDS traffic only (see hipnlp.hip): the copy-out tables prefetched into registers stay in flight across it
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // tables, parameters and the pose's variables -> LDS (ends with a workgroup barrier)
 struct PoseStageNoMid { __device__ __forceinline__ void operator()() const {} };
 template <class S, class T, class Mid = PoseStageNoMid> __device__ __forceinline__ void pose_stage(const PArgs& a, S& s, T& tabs, int b, int tid, Mid mid = Mid()) {
@@ -197,7 +195,7 @@ void hipnlp_pose_kernel(PArgs a) {
     PoseEm<TERRAIN> em{s.g, s.jac, s.jac - (js::V0 - pjs::DSLOTS)};
     Ctx<PoseEm<TERRAIN>> cx(s, tabs.kt, tabs.ks, tabs.gp, ki, em, &tb.head.kt, a.gp + b);   // (full tables: global memory)
     cx.hands = pose_hands(s, tabs);
-    // (one contiguous program instance per wave, as in hipnlp_knot_kernel: no wave jumps over the other waves' code)
+    // (one contiguous program instance per wave, see knot_stage.h dispatch_wave: no wave jumps over the other waves' code)
 #ifdef HIPNLP_STAMPS
 #define DEV_R(w, w8, fn, nt) if constexpr ((w) == W) { for (int t_ = lane; t_ < (nt); t_ += 64) fn(cx, t_); if (st_nt < 24) st_task[st_nt++] = __builtin_amdgcn_s_memtime(); }
 #define DEV_BARRIER st_arr[st_nb] = __builtin_amdgcn_s_memtime(); lds_barrier(); st_dep[st_nb] = __builtin_amdgcn_s_memtime(); st_nb++;
@@ -213,7 +211,7 @@ void hipnlp_pose_kernel(PArgs a) {
         constexpr int W = decltype(wc)::value;
         HIPNLP_POSE_PROGRAM(DEV_R, DEV_BARRIER)
     };
-    switch (wave) {
+    switch (wave) {   // (on the per-lane value, as these kernels always have: the scalar switch of dispatch_wave lays their instances out anew)
         case 0: run_wave(std::integral_constant<int, 0>{}); break;
         case 1: run_wave(std::integral_constant<int, 1>{}); break;
         case 2: run_wave(std::integral_constant<int, 2>{}); break;
@@ -309,7 +307,7 @@ void hipnlp_pose_hess_kernel(PArgs a) {
     Ctx<PoseHessEm<TERRAIN>> cx(s, tabs.kt, tabs.ks, tabs.gp, ki, em, &tb.head.kt, a.gp + b);
     cx.hands = pose_hands(s, tabs);
     HCtx<PoseHessEm<TERRAIN>> hcx{cx, hx};
-    // (one contiguous program instance per wave, as in hipnlp_knot_kernel: no wave jumps over the other waves' code)
+    // (one contiguous program instance per wave, see knot_stage.h dispatch_wave: no wave jumps over the other waves' code)
 #ifdef HIPNLP_STAMPS
 #define DEV_KIN(w, fn, nt) if constexpr ((w) == W) { for (int t_ = lane; t_ < (nt); t_ += 64) fn(cx, t_); if (st_nt < 24) st_task[st_nt++] = __builtin_amdgcn_s_memtime(); }
 #define DEV_RH(w, fn, nt) if constexpr ((w) == W) { for (int t_ = lane; t_ < (nt); t_ += 64) fn(hcx, t_); if (st_nt < 24) st_task[st_nt++] = __builtin_amdgcn_s_memtime(); }
@@ -323,7 +321,7 @@ void hipnlp_pose_hess_kernel(PArgs a) {
         constexpr int W = decltype(wc)::value;
         HIPNLP_POSE_HESS_PROGRAM(DEV_KIN, DEV_RH, DEV_BARRIER)
     };
-    switch (wave) {
+    switch (wave) {   // (on the per-lane value, as these kernels always have: the scalar switch of dispatch_wave lays their instances out anew)
         case 0: run_wave(std::integral_constant<int, 0>{}); break;
         case 1: run_wave(std::integral_constant<int, 1>{}); break;
         case 2: run_wave(std::integral_constant<int, 2>{}); break;

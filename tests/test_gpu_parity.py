@@ -590,7 +590,8 @@ def test_sharded_callback_reassembly_on_gpu(model, HipNlp, lifted, compact):
 def test_launch_number_wrap(model, HipNlp):
     """The launch number tags the published cost partials and is the generation of the non-finite flags; at 2^31 - 1 it starts
     over (flags and tags cleared).  HIPNLP_DEBUG_SEQ0 starts the count just below: evaluations across the wrap give bitwise the
-    values of a fresh handle, and a non-finite x is still reported on both sides of it."""
+    values of a fresh handle, and a non-finite x is still reported on both sides of it — by the host path (eval, eval_hess) and by
+    the device entry points that count launches of their own (eval_lagrangian_grad_device, eval_hess_vec_device)."""
     import os
     from hippopt_amd.hipnlp import HipNlpError
     st = periodic_step_settings(8, model)
@@ -614,6 +615,33 @@ def test_launch_number_wrap(model, HipNlp):
     hv_ref = ref.eval_hess(x, 1.0, np.ones((2, ref.m)))
     for _ in range(6):
         assert np.array_equal(eng.eval_hess(x, 1.0, np.ones((2, eng.m))), hv_ref)
+    # the one-launch device entry points number their launches themselves (the Lagrangian gradient with the callbacks' count, the
+    # Hessian-vector product with the Hessian's): six calls each across the wrap, a NaN in x before it and behind it.  They report a
+    # non-finite x in their result: NaNs in the trajectory that has one, the other trajectory untouched.
+    from test_gpu_hessian_vector import hvp
+    from test_gpu_lagrangian_grad import lgrad
+    rng = np.random.RandomState(11)
+    sigma, lam, v = np.array([1.0, 0.6]), rng.standard_normal((2, ref.m)), rng.standard_normal((2, ref.n))
+    calls = {"lgrad": lambda e, xi: lgrad(e, xi, sigma, lam), "hvp": lambda e, xi: hvp(e, xi, sigma, lam, v)}
+    bad = x.copy()
+    bad[1, 120:189] = np.nan   # (base, joints, centroidal variables of the first knot: jac g and the Hessian both depend on them)
+    want = {name: [call(ref, xi) for xi in (x, x2, bad)] for name, call in calls.items()}
+    for name in calls:
+        assert np.all(np.isfinite(want[name][0])) and np.all(np.isfinite(want[name][1])), name
+        assert np.all(np.isfinite(want[name][2][0])) and np.any(np.isnan(want[name][2][1])), name
+    with diag_overrides(HIPNLP_DEBUG_SEQ0=2 ** 31 - 3) as lib:
+        eng = HipNlp(st, model, batch=2, library=lib)
+    eng.set_params(p)
+    for name, call in calls.items():
+        for i in range(6):   # launches 2^31 - 2, (NaN: 2^31 - 1,) then 1, 2, 3, (NaN: 4,) 5, 6
+            assert np.array_equal(call(eng, (x, x2)[i % 2]), want[name][i % 2]), (name, i)
+            if i in (0, 3):
+                got = call(eng, bad)
+                assert np.array_equal(got[0], want[name][2][0]) and np.any(np.isnan(got[1])), (name, i)
+                assert np.array_equal(got.view(np.int64), want[name][2].view(np.int64)), (name, i)
+    # (and the host path of the same handle, whose flags share those generations, reports nothing stale behind them)
+    assert all(np.array_equal(a, b_) for a, b_ in zip(eng.eval(x), r1))
+    assert np.array_equal(eng.eval_hess(x, 1.0, np.ones((2, eng.m))), hv_ref)
 
 
 def test_hessian_values_straight_into_a_registered_array(model, HipNlp):

@@ -92,3 +92,30 @@ def test_four_wave_vary_kernels_fit_five_workgroups_per_cu(res, terrain):
     assert r["wg"] == 256 and r["scratch"] == 0
     assert 5 * r["lds"] <= LDS_PER_CU, r
     assert _granule(r["vgpr"] + r["agpr"]) * 5 <= VGPR_FILE, r
+
+
+# The Lagrangian-gradient kernel (hipnlp.hip hipnlp_knot_lgrad_kernel) keeps the occupancy of the four-wave callback kernel it derives
+# from: 256 threads, no scratch, four workgroups per CU on both terrains.
+@pytest.mark.parametrize("terrain", [0, 1])
+def test_lagrangian_gradient_kernel_fits_four_workgroups_per_cu(res, terrain):
+    r = res["hipnlp_knot_lgrad_kernel<%d>" % terrain]
+    assert r["wg"] == 256 and r["scratch"] == 0, r
+    assert 4 * (-(-r["lds"] // 1280)) * 1280 <= LDS_PER_CU, r          # (LDS is handed out in granules of 1 280 B)
+    assert (r["vgpr"] + r["agpr"] + 7) // 8 * 8 * 4 <= VGPR_FILE, r     # four waves per SIMD
+
+
+# The fused Hessian-vector kernel (hipnlp.hip hipnlp_knot_hvp_kernel) keeps the occupancy of the compact Hessian kernel it derives from:
+# 256 threads, no scratch, three workgroups per CU by LDS granules and by registers on both terrains; the stored-values kernel uses no
+# scratch.
+@pytest.mark.parametrize("terrain", [0, 1])
+def test_fused_kernel_fits_three_workgroups_per_cu(res, terrain):
+    r = res["hipnlp_knot_hvp_kernel<%d>" % terrain]
+    assert r["wg"] == 256 and r["scratch"] == 0, r
+    assert 3 * (-(-r["lds"] // 1280)) * 1280 <= LDS_PER_CU, r          # (LDS is handed out in granules of 1 280 B)
+    assert (r["vgpr"] + r["agpr"] + 7) // 8 * 8 * 3 <= VGPR_FILE, r     # three waves per SIMD
+    assert r["lds"] <= res["hipnlp_knot_hess_kernel<%d,1>" % terrain]["lds"], r   # no more LDS than the compact Hessian kernel
+
+
+def test_stored_values_kernel_uses_no_scratch(res):
+    r = res["hipnlp_hess_times_kernel"]
+    assert r["wg"] == 256 and r["scratch"] == 0, r
