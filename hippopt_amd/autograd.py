@@ -20,15 +20,29 @@ create_graph=True) through nlp(x), record it; without create_graph the backward 
 of the Lagrangian gradient with respect to sigma and lam are grad f . w and J w: the engine has no Jacobian-vector product, so a double
 backward that needs them — a loss that is not linear in f and g, e.g. (f ** 2).sum(), or a sigma / lam that requires grad — raises
 NotImplementedError instead of returning zeros.  No third derivative; no derivative with respect to the parameters.
+
+The static pose finder, a batch of B independent poses, has the same interface and is complete to second order:
+
+    nlp = PoseNLP(settings, model, batch=B)                # one pose handle (hipnlp_pose_create) on cuda:`device`
+    nlp.set_params(p)                                      # [B, 202]
+    f, g = nlp(x)                                          # x: [B, 81] -> f [B], g [B, m]
+    gx = nlp.lagrangian_gradient(x, sigma, lam)            # ONE launch (hipnlp_pose_eval_lagrangian_grad_device)
+    dot, jv = nlp.jacobian_vector_product(x, v)            # grad f . v [B], J v [B, m], ONE launch (hipnlp_pose_eval_jac_vec_device)
+    hv = nlp.hessian_vector_product(x, sigma, lam, v)      # ONE launch (hipnlp_pose_eval_hess_vec_device)
+
+A pose is one workgroup, which holds all of jac g and of the Hessian in LDS: the derivatives of the Lagrangian gradient with respect to
+sigma and lam, grad f . w and J w, are one launch too, so a double backward through any loss in f and g — (f ** 2).sum() + (g ** 2).sum()
+— runs: H w from one launch when x needs it, grad f . w and J w from one launch when sigma or lam needs it.  Nothing raises.
 torch is imported when first needed."""
 import numbers
 
 import numpy as np
 
-from .hipnlp import HipNlp
+from .hipnlp import HipNlp, HipPose
 
 _FUNCTION = None
 _LGRAD_FUNCTION = None
+_POSE_LGRAD_FUNCTION = None
 
 
 def _torch():
@@ -59,7 +73,7 @@ def _function():
                 sigma = df.to(torch.float64).contiguous() if df is not None else torch.zeros(nlp.batch, dtype=torch.float64, device=x.device)
                 lam = dg.to(torch.float64).contiguous() if dg is not None else torch.zeros(nlp.batch, nlp.m, dtype=torch.float64, device=x.device)
                 if torch.is_grad_enabled():   # (create_graph=True: the same launch, recorded, so that it can be differentiated in x)
-                    return _lgrad_function().apply(x, sigma, lam, nlp), None
+                    return nlp._recorded_lgrad().apply(x, sigma, lam, nlp), None
                 return nlp._launch(x, sigma, lam), None
 
         _FUNCTION = NLPFunction
@@ -97,6 +111,37 @@ def _lgrad_function():
     return _LGRAD_FUNCTION
 
 
+def _pose_lgrad_function():
+    """the pose finder's Lagrangian gradient as a torch.autograd.Function of (x, sigma, lam): its backward pass returns all three
+    derivatives — H w in x (one launch), grad f . w in sigma and J w in lam (one launch for both)"""
+    global _POSE_LGRAD_FUNCTION
+    if _POSE_LGRAD_FUNCTION is None:
+        torch = _torch()
+        from torch.autograd.function import once_differentiable
+
+        class PoseLagrangianGradFunction(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x, sigma, lam, nlp):
+                ctx.save_for_backward(x, sigma, lam)
+                ctx.nlp = nlp
+                return nlp._launch(x.detach(), sigma.detach(), lam.detach())
+
+            @staticmethod
+            @once_differentiable
+            def backward(ctx, w):
+                x, sigma, lam = ctx.saved_tensors
+                nlp = ctx.nlp
+                w = w.to(torch.float64).contiguous()
+                gx = nlp._launch_hvp(x, sigma, lam, w) if ctx.needs_input_grad[0] else None
+                gs = gl = None
+                if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+                    gs, gl = nlp._launch_jvp(x, w, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+                return gx, gs, gl, None
+
+        _POSE_LGRAD_FUNCTION = PoseLagrangianGradFunction
+    return _POSE_LGRAD_FUNCTION
+
+
 class HessianValues:
     """The Hessian of the Lagrangian of every trajectory at one (x, sigma, lam), as the value run `values` [batch, nnz_h] of
     hipnlp_eval_hess_device (pattern: engine.hess_sparsity()); matvec(v) multiplies it by v [batch, n] in one launch
@@ -113,14 +158,9 @@ class HessianValues:
         return out
 
 
-class KinodynamicNLP:
-    """(f, g) = nlp(x) on a [batch, n] float64 tensor of cuda:`device`, differentiable in x.  detect_simple_bounds: the reduced NLP
-    (HIPNLP_FLAG_DETECT_SIMPLE_BOUNDS): g and lambda have the m rows of that problem."""
-
-    def __init__(self, settings, model, batch, device=0, detect_simple_bounds=False):
-        self.engine = HipNlp(settings, model, batch=batch, device=device, detect_simple_bounds=detect_simple_bounds)
-        self.batch, self.n, self.m, self.np = self.engine.batch, self.engine.n, self.engine.m, self.engine.np
-        self.device_index = int(device)
+class _DeviceNLP:
+    """what the two NLPs share: an engine handle on cuda:`device_index` with batch, n, m, np; tensors checked to be float64, contiguous and
+    on that device; launches ordered on torch.cuda.current_stream()"""
 
     @property
     def device(self):
@@ -131,6 +171,52 @@ class KinodynamicNLP:
         if hasattr(p, "detach"):
             p = p.detach().cpu().numpy()
         self.engine.set_params(np.asarray(p, dtype=np.float64))
+
+    def _sigma(self, sigma):
+        if isinstance(sigma, numbers.Real):
+            sigma = _torch().full((self.batch,), float(sigma), dtype=_torch().float64, device=self.device)
+        self._check("sigma", sigma, (self.batch,))
+        return sigma
+
+    def _on_current_stream(self, launch):
+        """launch(stream handle), ordered on torch.cuda.current_stream().  A NULL stream means the handle's OWN stream to the library
+        (include/hipnlp.h), so on torch's default stream the launch goes to a private stream that waits for the current one, and the
+        current one waits for it (tensors are allocated on the current stream: nothing of it runs before the launch has ended)."""
+        torch = _torch()
+        cur = torch.cuda.current_stream(self.device)
+        if cur.cuda_stream:
+            launch(cur.cuda_stream)
+            return
+        if getattr(self, "_side", None) is None:
+            self._side = torch.cuda.Stream(device=self.device)
+        self._side.wait_stream(cur)
+        launch(self._side.cuda_stream)
+        cur.wait_stream(self._side)
+
+    def _check(self, name, t, shape):
+        torch = _torch()
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("%s: a torch.Tensor, not %s" % (name, type(t).__name__))
+        if t.dtype != torch.float64:
+            raise TypeError("%s: dtype float64, not %s" % (name, t.dtype))
+        if t.device != self.device:
+            raise ValueError("%s: on %s, not %s" % (name, self.device, t.device))
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("%s: shape %s, not %s" % (name, tuple(shape), tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("%s: a contiguous tensor" % name)
+
+
+class KinodynamicNLP(_DeviceNLP):
+    """(f, g) = nlp(x) on a [batch, n] float64 tensor of cuda:`device`, differentiable in x.  detect_simple_bounds: the reduced NLP
+    (HIPNLP_FLAG_DETECT_SIMPLE_BOUNDS): g and lambda have the m rows of that problem."""
+
+    _recorded_lgrad = staticmethod(_lgrad_function)
+
+    def __init__(self, settings, model, batch, device=0, detect_simple_bounds=False):
+        self.engine = HipNlp(settings, model, batch=batch, device=device, detect_simple_bounds=detect_simple_bounds)
+        self.batch, self.n, self.m, self.np = self.engine.batch, self.engine.n, self.engine.m, self.engine.np
+        self.device_index = int(device)
 
     def __call__(self, x):
         """(f [batch], g [batch, m]); differentiable in x"""
@@ -148,12 +234,6 @@ class KinodynamicNLP:
         if x.requires_grad and torch.is_grad_enabled():   # (differentiable in x: the backward pass is the Hessian-vector product)
             return _lgrad_function().apply(x, sigma, lam, self)
         return self._launch(x, sigma, lam)
-
-    def _sigma(self, sigma):
-        if isinstance(sigma, numbers.Real):
-            sigma = _torch().full((self.batch,), float(sigma), dtype=_torch().float64, device=self.device)
-        self._check("sigma", sigma, (self.batch,))
-        return sigma
 
     def hessian_vector_product(self, x, sigma, lam, v):
         """H(x, sigma, lam) v per trajectory ([batch, n]), H the Hessian of sigma f + lam . g in x: sigma a number or a [batch] tensor,
@@ -175,21 +255,6 @@ class KinodynamicNLP:
         return HessianValues(self, values)
 
     # ---- internals ------------------------------------------------------------------------------------------------------------------
-    def _on_current_stream(self, launch):
-        """launch(stream handle), ordered on torch.cuda.current_stream().  A NULL stream means the handle's OWN stream to the library
-        (include/hipnlp.h), so on torch's default stream the launch goes to a private stream that waits for the current one, and the
-        current one waits for it (tensors are allocated on the current stream: nothing of it runs before the launch has ended)."""
-        torch = _torch()
-        cur = torch.cuda.current_stream(self.device)
-        if cur.cuda_stream:
-            launch(cur.cuda_stream)
-            return
-        if getattr(self, "_side", None) is None:
-            self._side = torch.cuda.Stream(device=self.device)
-        self._side.wait_stream(cur)
-        launch(self._side.cuda_stream)
-        cur.wait_stream(self._side)
-
     def _forward(self, x, f, g):
         self._on_current_stream(lambda s: self.engine.eval_device(x.data_ptr(), f.data_ptr(), 0, g.data_ptr(), 0, stream=s))
 
@@ -203,15 +268,67 @@ class KinodynamicNLP:
         self._on_current_stream(lambda s: self.engine.eval_hess_vec_device(x.data_ptr(), sigma.data_ptr(), lam.data_ptr(), v.data_ptr(), out.data_ptr(), stream=s))
         return out
 
-    def _check(self, name, t, shape):
+
+class PoseNLP(_DeviceNLP):
+    """(f, g) = nlp(x) of `batch` independent static poses on a [batch, 81] float64 tensor of cuda:`device`, differentiable in x to
+    second order (module docstring).  Parameters are per pose: set_params takes [batch, 202]."""
+
+    _recorded_lgrad = staticmethod(_pose_lgrad_function)
+
+    def __init__(self, settings, model, batch, device=0):
+        self.engine = HipPose(settings, model, batch=batch, device=device)
+        self.batch, self.n, self.m, self.np = self.engine.batch, self.engine.n, self.engine.m, self.engine.np
+        self.device_index = int(device)
+
+    def __call__(self, x):
+        """(f [batch], g [batch, m]); differentiable in x"""
+        self._check("x", x, (self.batch, self.n))
+        return _function().apply(x, self)
+
+    def lagrangian_gradient(self, x, sigma, lam):
+        """sigma grad f(x) + J(x)^T lam per pose ([batch, 81]): sigma a number or a [batch] tensor, lam [batch, m].  Differentiable in x,
+        sigma and lam where they require grad."""
         torch = _torch()
-        if not isinstance(t, torch.Tensor):
-            raise TypeError("%s: a torch.Tensor, not %s" % (name, type(t).__name__))
-        if t.dtype != torch.float64:
-            raise TypeError("%s: dtype float64, not %s" % (name, t.dtype))
-        if t.device != self.device:
-            raise ValueError("%s: on %s, not %s" % (name, self.device, t.device))
-        if tuple(t.shape) != tuple(shape):
-            raise ValueError("%s: shape %s, not %s" % (name, tuple(shape), tuple(t.shape)))
-        if not t.is_contiguous():
-            raise ValueError("%s: a contiguous tensor" % name)
+        self._check("x", x, (self.batch, self.n))
+        sigma = self._sigma(sigma)
+        self._check("lam", lam, (self.batch, self.m))
+        if (x.requires_grad or sigma.requires_grad or lam.requires_grad) and torch.is_grad_enabled():
+            return _pose_lgrad_function().apply(x, sigma, lam, self)
+        return self._launch(x, sigma, lam)
+
+    def jacobian_vector_product(self, x, v):
+        """(grad f(x) . v [batch], J(x) v [batch, m]) per pose, v [batch, 81].  One launch; jac g is never written.  Not recorded by autograd."""
+        self._check("x", x, (self.batch, self.n))
+        self._check("v", v, (self.batch, self.n))
+        return self._launch_jvp(x, v, True, True)
+
+    def hessian_vector_product(self, x, sigma, lam, v):
+        """H(x, sigma, lam) v per pose ([batch, 81]), H the Hessian of sigma f + lam . g in x: sigma a number or a [batch] tensor,
+        lam [batch, m], v [batch, 81].  One launch; H is never written.  Not recorded by autograd."""
+        self._check("x", x, (self.batch, self.n))
+        sigma = self._sigma(sigma)
+        self._check("lam", lam, (self.batch, self.m))
+        self._check("v", v, (self.batch, self.n))
+        return self._launch_hvp(x, sigma, lam, v)
+
+    # ---- internals ------------------------------------------------------------------------------------------------------------------
+    def _forward(self, x, f, g):
+        self._on_current_stream(lambda s: self.engine.eval_device(x.data_ptr(), f.data_ptr(), 0, g.data_ptr(), 0, stream=s))
+
+    def _launch(self, x, sigma, lam):
+        out = _torch().empty_like(x, memory_format=_torch().contiguous_format)
+        self._on_current_stream(lambda s: self.engine.eval_lagrangian_grad_device(x.data_ptr(), sigma.data_ptr(), lam.data_ptr(), out.data_ptr(), stream=s))
+        return out
+
+    def _launch_jvp(self, x, v, want_dot, want_jv):
+        torch = _torch()
+        dot = torch.empty(self.batch, dtype=torch.float64, device=x.device) if want_dot else None
+        jv = torch.empty(self.batch, self.m, dtype=torch.float64, device=x.device) if want_jv else None
+        self._on_current_stream(lambda s: self.engine.eval_jac_vec_device(x.data_ptr(), v.data_ptr(), dot.data_ptr() if want_dot else 0,
+                                                                          jv.data_ptr() if want_jv else 0, stream=s))
+        return dot, jv
+
+    def _launch_hvp(self, x, sigma, lam, v):
+        out = _torch().empty_like(x, memory_format=_torch().contiguous_format)
+        self._on_current_stream(lambda s: self.engine.eval_hess_vec_device(x.data_ptr(), sigma.data_ptr(), lam.data_ptr(), v.data_ptr(), out.data_ptr(), stream=s))
+        return out

@@ -19,6 +19,7 @@
 
 #include "knot_stage.h"
 #include "pose_layout.h"
+#include "pose_products.h"
 
 // (hipnlp.hip: hipMemcpy that survives a host buffer inside a stale self-registered range)
 extern "C" hipError_t hipnlp_internal_memcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
@@ -346,6 +347,195 @@ void hipnlp_pose_hess_kernel(PArgs a) {
 #endif
 }
 
+// =====================================================================================================================
+// The pose finder's products are workgroup-local (pose_products.h): a pose is ONE workgroup, which holds every entry of jac g in the cut
+// staging when the pose program ends and every entry of the Hessian of the Lagrangian in hx.H when the Hessian program ends.  The three
+// kernels below run those two programs unchanged — the same scratch, the same emitters, the same bits — and replace the copy-out by sums
+// over the directories of PoseLayout::build_product_tables, one column / row / variable per thread: no atomics, no second pass, a fixed
+// order.  81 (or m + 1) doubles leave per pose instead of up to 1 024 + m + 81 (or hnnz); neither jac g nor H is ever written.
+// =====================================================================================================================
+struct PPArgs {
+    PArgs p;                    // what the pose kernels take: tables, x, parameters, flags; sigma, lambda and m as the Hessian kernel
+    const PoseProdTables* pt;
+    const double* v;            // [batch][81]       direction (jvp, hvp)
+    double* out;                // [batch][81]       xbar (lgrad), H v (hvp);  [batch][m] J v (jvp) or null
+    double* dot;                // [batch]           grad f . v (jvp) or null
+};
+constexpr int PP_LGRAD = 0, PP_JVP = 1;
+// (a staging functor of their own, nothing to do in it: with PoseStageNoMid the first-order kernels would share hipnlp_pose_kernel's
+//  instantiation of pose_stage, and the compiler then lays that kernel's staging out differently — same registers, other instructions)
+struct PoseStageProducts { __device__ __forceinline__ void operator()() const {} };
+constexpr int PP_EW = PP_ENT_CAP / WG, PP_TW = PP_TOUCH_CAP / WG;
+constexpr int PP_DOT_THREAD = WG - 1;   // the lane that sums grad f . v (m = 89 .. 104 rows: a thread of the fourth wave, which sums no row)
+static_assert(PP_WG == WG && PP_ENT_CAP == POSE_MAX_NNZ && PP_ROW_CAP == POSE_MAX_M, "pose_products.h counts in workgroups of this file");
+
+// Where the first-order kernels stage once the pose program has ended.  Nothing reads the scratch then but the sums, which need grad and
+// jac (these kernels store no g and no cost term): the multipliers / the direction go on the joint records and own[] (one union: read by
+// the forward kinematics and the composites, phases two to four), the entry words on Rw, ow, aw and comp (contiguous doubles: the last
+// reader of the kinematic arrays is the consistency-row phase, whose barrier is the program's last).
+template <class S> __device__ __forceinline__ double* pose_factor_stage(S& s) { return lgrad_lam_stage(s); }
+template <class S> __device__ __forceinline__ int32_t* pose_word_stage(S& s) { return reinterpret_cast<int32_t*>(&s.Rw[0][0]); }
+
+// MODE PP_LGRAD: xbar = sigma grad f + J^T lambda, one thread per column.  MODE PP_JVP: J v, one thread per row, and grad f . v on one lane.
+template <int TERRAIN, int MODE, class Scratch, class Tabs> __device__ __forceinline__ void pose_first_order(const PPArgs& pa, Scratch& s, Tabs& tabs) {
+    static_assert(std::is_same_v<Scratch, typename PoseEm<TERRAIN>::Scratch>, "the emitter names the scratch the tasks run on");
+    static_assert(PP_ROW_CAP * sizeof(double) <= sizeof(ScratchJrOwn<LAYOUT_COMPACT_NOG>), "multipliers / direction on the joint records");
+    static_assert(offsetof(Scratch, comp) + sizeof(Scratch::comp) - offsetof(Scratch, Rw) >= PP_ENT_CAP * sizeof(int32_t) && offsetof(Scratch, comp) < offsetof(Scratch, grad), "entry words on Rw .. comp");
+    const PArgs& a = pa.p;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int b = blockIdx.x;
+    const PoseTables& tb = *a.tb;
+    const PoseProdTables& pt = *pa.pt;
+    // the factor of this thread (the multiplier of ROW tid / element tid of v), sigma, the entry words and this thread's directory word:
+    // independent loads, in flight together with the staging loads (as hipnlp_pose_hess_kernel loads its multipliers)
+    const int m = a.m;
+    double fac = 0.0, sig = 0.0;
+    if constexpr (MODE == PP_LGRAD) { if (tid < m) fac = a.lambda[size_t(b) * m + tid]; sig = a.sigma[b]; }
+    else { if (tid < POSE_NX) fac = pa.v[size_t(b) * POSE_NX + tid]; }
+    int32_t w[PP_EW];
+#pragma unroll
+    for (int it = 0; it < PP_EW; ++it) w[it] = (MODE == PP_LGRAD ? pt.col_word : pt.row_word)[tid + it * WG];
+    const int32_t dir = (MODE == PP_LGRAD ? pt.col_dir : pt.row_dir)[tid];
+    pose_stage(a, s, tabs, b, tid, PoseStageProducts());
+
+    KnotInfo ki{1, 3, 0, 0};
+    PoseEm<TERRAIN> em{s.g, s.jac, s.jac - (js::V0 - pjs::DSLOTS)};
+    Ctx<PoseEm<TERRAIN>> cx(s, tabs.kt, tabs.ks, tabs.gp, ki, em, &tb.head.kt, a.gp + b);
+    cx.hands = pose_hands(s, tabs);
+#define DEV_R(w, w8, fn, nt) if constexpr ((w) == W) { for (int t_ = lane; t_ < (nt); t_ += 64) fn(cx, t_); }
+#define DEV_BARRIER lds_barrier();
+    auto run_wave = [&](auto wc) __attribute__((always_inline)) {
+        constexpr int W = decltype(wc)::value;
+        HIPNLP_POSE_PROGRAM(DEV_R, DEV_BARRIER)
+    };
+    switch (wave) {   // (as hipnlp_pose_kernel: the same program instances)
+        case 0: run_wave(std::integral_constant<int, 0>{}); break;
+        case 1: run_wave(std::integral_constant<int, 1>{}); break;
+        case 2: run_wave(std::integral_constant<int, 2>{}); break;
+        default: run_wave(std::integral_constant<int, 3>{}); break;
+    }
+#undef DEV_R
+#undef DEV_BARRIER
+    // ---- the program has ended (its last barrier is behind it): factors and entry words into dead scratch, then the sums
+    double* fs = pose_factor_stage(s);
+    int32_t* ws = pose_word_stage(s);
+    fs[tid] = fac;
+#pragma unroll
+    for (int it = 0; it < PP_EW; ++it) ws[tid + it * WG] = w[it];
+    lds_barrier();
+    int bad = 0;
+    if constexpr (MODE == PP_LGRAD) {
+        if (tid < POSE_NX) {
+            const double xb = pose_xbar_column(sig, s.grad[pose_to_knot_col(tid)], dir, ws, fs, s.jac);
+            bad = !isfinite(xb);
+            pa.out[size_t(b) * POSE_NX + tid] = xb;
+        }
+    } else {
+        const double y = pose_jv_row(dir, ws, fs, s.jac);                                   // (behind m: an empty range, +0.0)
+        const double d = tid == PP_DOT_THREAD ? pose_gradf_dot_v(s.grad, fs) : 0.0;
+        bad = int(!isfinite(y)) | int(!isfinite(d));
+        if (pa.out && tid < m) pa.out[size_t(b) * m + tid] = y;
+        if (pa.dot && tid == PP_DOT_THREAD) pa.dot[b] = d;
+    }
+    const int anybad = pose_vote(tabs, bad, lane);
+    if (tid == 0) a.flags[b] = anybad;
+}
+
+// Occupancy of hipnlp_pose_kernel, whose program and scratch these are: planar terrain five workgroups per CU, smooth steps four.
+template <int TERRAIN> __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(TERRAIN == HIPNLP_TERRAIN_PLANAR ? 5 : 4, TERRAIN == HIPNLP_TERRAIN_PLANAR ? 5 : 4)))
+void hipnlp_pose_lgrad_kernel(PPArgs pa) {
+    using Scratch = PoseScratchT<TERRAIN>;
+    __shared__ Scratch s;
+    __shared__ PoseSharedT<Scratch::trimmed> tabs;
+    static_assert(sizeof(Scratch) + sizeof(PoseSharedT<Scratch::trimmed>) <= (TERRAIN == HIPNLP_TERRAIN_PLANAR ? 32000 : 40960), "five / four workgroups per CU");
+    pose_first_order<TERRAIN, PP_LGRAD>(pa, s, tabs);
+}
+template <int TERRAIN> __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(TERRAIN == HIPNLP_TERRAIN_PLANAR ? 5 : 4, TERRAIN == HIPNLP_TERRAIN_PLANAR ? 5 : 4)))
+void hipnlp_pose_jvp_kernel(PPArgs pa) {
+    using Scratch = PoseScratchT<TERRAIN>;
+    __shared__ Scratch s;
+    __shared__ PoseSharedT<Scratch::trimmed> tabs;
+    static_assert(sizeof(Scratch) + sizeof(PoseSharedT<Scratch::trimmed>) <= (TERRAIN == HIPNLP_TERRAIN_PLANAR ? 32000 : 40960), "five / four workgroups per CU");
+    pose_first_order<TERRAIN, PP_JVP>(pa, s, tabs);
+}
+
+// H(x, sigma, lambda) v: what hipnlp_pose_hess_kernel runs — the scratch without grad and jac, hx, the multiplier scatter between the two
+// staging barriers, the Hessian program — and then one variable per thread over its touches instead of the copy-out through hperm.
+// The touch words, this thread's directory word and its element of v are fetched behind the last barrier but one (in flight across the
+// last phase, their registers free before it) and staged over the knot scratch s_raw once the program has ended: every member of it is
+// kinematics or a parameter record by then, read by no one; hx (lam, Y, qq, H) is not touched.
+constexpr int POSE_HESS_BARRIERS = 6, POSE_HVP_TABLES_AT = POSE_HESS_BARRIERS - 1;
+template <int TERRAIN> __global__ __launch_bounds__(WG) __attribute__((amdgpu_waves_per_eu(TERRAIN == HIPNLP_TERRAIN_PLANAR ? 5 : 3, TERRAIN == HIPNLP_TERRAIN_PLANAR ? 5 : 3)))
+void hipnlp_pose_hvp_kernel(PPArgs pa) {
+    using Scratch = typename PoseHessEm<TERRAIN>::Scratch;
+    constexpr size_t S_WORDS = offsetof(Scratch, grad) / sizeof(double);
+    __shared__ alignas(16) double s_raw[S_WORDS];
+    Scratch& s = *reinterpret_cast<Scratch*>(s_raw);
+    __shared__ PoseSharedT<Scratch::trimmed> tabs;
+    __shared__ HessScratch hx;
+    constexpr size_t TW_WORDS = PP_TOUCH_CAP * sizeof(int32_t) / sizeof(double);
+    static_assert(TW_WORDS + PP_WG <= S_WORDS && POSE_NX <= PP_WG, "touch words and v on the dead knot scratch");
+    const PArgs& a = pa.p;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int b = blockIdx.x;
+    const PoseTables& tb = *a.tb;
+    const PoseProdTables& pt = *pa.pt;
+    // (the multipliers: as hipnlp_pose_hess_kernel)
+    const int m = a.m;
+    double lam_i = 0.0, sig = 0.0;
+    int slot_i = -1;
+    if (tid < m) { lam_i = a.lambda[size_t(b) * m + tid]; slot_i = tb.row_slot[tid]; }
+    if (tid == 0) sig = a.sigma[b];
+    for (int slot = tid; slot < gs::COUNT; slot += WG) hx.lam[slot] = 0.0;
+    pose_stage(a, s, tabs, b, tid, [&]() { if (slot_i >= 0) hx.lam[slot_i] = lam_i; if (tid == 0) hx.sigma = sig; });
+
+    int32_t w[PP_TW], dir = 0;
+    double vi = 0.0;
+    auto fetch_tables = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int it = 0; it < PP_TW; ++it) w[it] = pt.touch_word[tid + it * WG];
+        dir = pt.var_dir[tid];
+        if (tid < POSE_NX) vi = pa.v[size_t(b) * POSE_NX + tid];
+    };
+    int bar = 0;   // barriers passed (the program is straight-line code: a constant at every use)
+    KnotInfo ki{1, 3, 0, 0};
+    PoseHessEm<TERRAIN> em{nullptr, nullptr, hx.H};   // (no task of the Hessian program emits a row or a Jacobian entry)
+    Ctx<PoseHessEm<TERRAIN>> cx(s, tabs.kt, tabs.ks, tabs.gp, ki, em, &tb.head.kt, a.gp + b);
+    cx.hands = pose_hands(s, tabs);
+    HCtx<PoseHessEm<TERRAIN>> hcx{cx, hx};
+#define DEV_KIN(w, fn, nt) if constexpr ((w) == W) { for (int t_ = lane; t_ < (nt); t_ += 64) fn(cx, t_); }
+#define DEV_RH(w, fn, nt) if constexpr ((w) == W) { for (int t_ = lane; t_ < (nt); t_ += 64) fn(hcx, t_); }
+#define DEV_BARRIER lds_barrier(); if (++bar == POSE_HVP_TABLES_AT) fetch_tables();
+    auto run_wave = [&](auto wc) __attribute__((always_inline)) {
+        constexpr int W = decltype(wc)::value;
+        HIPNLP_POSE_HESS_PROGRAM(DEV_KIN, DEV_RH, DEV_BARRIER)
+    };
+    switch (wave) {   // (as hipnlp_pose_hess_kernel: the same program instances)
+        case 0: run_wave(std::integral_constant<int, 0>{}); break;
+        case 1: run_wave(std::integral_constant<int, 1>{}); break;
+        case 2: run_wave(std::integral_constant<int, 2>{}); break;
+        default: run_wave(std::integral_constant<int, 3>{}); break;
+    }
+#undef DEV_KIN
+#undef DEV_RH
+#undef DEV_BARRIER
+    // ---- the program has ended (its last barrier is behind it): touch words and v over the dead knot scratch, then one variable per thread
+    int32_t* ws = reinterpret_cast<int32_t*>(s_raw);
+    double* vs = s_raw + TW_WORDS;
+#pragma unroll
+    for (int it = 0; it < PP_TW; ++it) ws[tid + it * WG] = w[it];
+    vs[tid] = vi;
+    lds_barrier();
+    int bad = 0;
+    if (tid < POSE_NX) {
+        const double y = pose_hv_row(dir, ws, vs, hx.H);
+        bad = !isfinite(y);
+        pa.out[size_t(b) * POSE_NX + tid] = y;
+    }
+    const int anybad = pose_vote(tabs, bad, lane);
+    if (tid == 0) a.flags[b] = anybad;
+}
+
 thread_local std::string g_pose_create_error;
 
 }  // namespace
@@ -360,6 +550,7 @@ struct hipnlp_pose_handle {
     bool timing_valid = false, params_set = false, have_result = false;
     bool time_host = false;   // hipnlp_pose_set_host_timing: the host-buffer calls bracket their launch with events (each record drains the stream: ~3 us of a 25 us call)
     PoseTables* d_tb = nullptr;
+    PoseProdTables* d_pt = nullptr;   // tables of the product kernels (pose_products.h): a block of their own, PoseTables is what it was
     double *d_x = nullptr, *d_pk = nullptr, *d_xr = nullptr, *d_f = nullptr, *d_grad = nullptr, *d_g = nullptr, *d_jac = nullptr, *d_cost = nullptr;
     GParams* d_gp = nullptr;
     int32_t* d_flags = nullptr;
@@ -393,7 +584,7 @@ static void pose_free_all(hipnlp_pose_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->dev);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* dptrs[] = {h->d_tb, h->d_x, h->d_pk, h->d_xr, h->d_f, h->d_grad, h->d_g, h->d_jac, h->d_cost, h->d_gp, h->d_flags, h->d_sigma, h->d_lambda, h->d_hess};
+    void* dptrs[] = {h->d_tb, h->d_pt, h->d_x, h->d_pk, h->d_xr, h->d_f, h->d_grad, h->d_g, h->d_jac, h->d_cost, h->d_gp, h->d_flags, h->d_sigma, h->d_lambda, h->d_hess};
     for (void* q : dptrs) if (q) (void)hipFree(q);
     void* hptrs[] = {h->h_x, h->h_f, h->h_grad, h->h_g, h->h_jac, h->h_cost, h->h_flags, h->h_sigma, h->h_lambda, h->h_hess};
     for (void* q : hptrs) if (q) (void)hipHostFree(q);
@@ -509,6 +700,14 @@ int hipnlp_pose_create(const hipnlp_pose_desc* desc, hipnlp_pose_handle** out) {
     hipError_t ce = hipnlp_internal_memcpy(h->d_tb, tb, sizeof(PoseTables), hipMemcpyHostToDevice);
     delete tb;
     if (ce != hipSuccess) return fail(HIPNLP_E_NODEVICE, std::string("hipMemcpy tables: ") + hipGetErrorString(ce));
+    {
+        CREATE_TRY(hipMalloc(&h->d_pt, sizeof(PoseProdTables)));
+        PoseProdTables* pt = new PoseProdTables();
+        h->L.fill_product_tables(*pt);
+        ce = hipnlp_internal_memcpy(h->d_pt, pt, sizeof(PoseProdTables), hipMemcpyHostToDevice);
+        delete pt;
+        if (ce != hipSuccess) return fail(HIPNLP_E_NODEVICE, std::string("hipMemcpy product tables: ") + hipGetErrorString(ce));
+    }
 #undef CREATE_TRY
     *out = h;
     return HIPNLP_OK;
@@ -655,6 +854,57 @@ int hipnlp_pose_eval_hess(hipnlp_pose_handle* h, const double* x, const double* 
     for (size_t b = 0; b < B; ++b)
         if (h->h_flags[b]) { h->err = "non-finite value produced by the evaluation"; return HIPNLP_E_NUMERIC; }
     return HIPNLP_OK;
+}
+
+// ---- workgroup-local products (pose_products.h): one launch each, device pointers, no host copy --------------------------------------
+enum { POSE_PROD_LGRAD, POSE_PROD_JVP, POSE_PROD_HVP };
+static int pose_product_launch(hipnlp_pose_handle* h, int which, const double* x_dev, const double* sigma_dev, const double* lambda_dev, const double* v_dev,
+                               double* out_dev, double* dot_dev, void* stream) {
+    if (!h->params_set) { h->err = "parameters not set (hipnlp_pose_set_params)"; return HIPNLP_E_PARAMS; }
+    HIP_TRY(h, hipSetDevice(h->dev));
+    h->have_result = false;
+    PPArgs pa{};
+    PArgs& a = pa.p;
+    a.tb = h->d_tb; a.x = x_dev; a.pk = h->d_pk; a.xr = h->d_xr; a.gp = h->d_gp;
+    a.cost_terms = h->d_cost; a.flags = h->d_flags;
+    a.sigma = sigma_dev; a.lambda = lambda_dev; a.m = h->L.m;
+    pa.pt = h->d_pt; pa.v = v_dev; pa.out = out_dev; pa.dot = dot_dev;
+    hipStream_t s = stream ? hipStream_t(stream) : h->stream;
+    const dim3 grid(unsigned(h->batch)), block(WG);
+    const bool planar = h->d.settings.terrain == HIPNLP_TERRAIN_PLANAR;
+    switch (which) {
+        case POSE_PROD_LGRAD:
+            if (planar) hipLaunchKernelGGL(hipnlp_pose_lgrad_kernel<HIPNLP_TERRAIN_PLANAR>, grid, block, 0, s, pa);
+            else hipLaunchKernelGGL(hipnlp_pose_lgrad_kernel<HIPNLP_TERRAIN_SMOOTH_STEPS>, grid, block, 0, s, pa);
+            break;
+        case POSE_PROD_JVP:
+            if (planar) hipLaunchKernelGGL(hipnlp_pose_jvp_kernel<HIPNLP_TERRAIN_PLANAR>, grid, block, 0, s, pa);
+            else hipLaunchKernelGGL(hipnlp_pose_jvp_kernel<HIPNLP_TERRAIN_SMOOTH_STEPS>, grid, block, 0, s, pa);
+            break;
+        default:
+            if (planar) hipLaunchKernelGGL(hipnlp_pose_hvp_kernel<HIPNLP_TERRAIN_PLANAR>, grid, block, 0, s, pa);
+            else hipLaunchKernelGGL(hipnlp_pose_hvp_kernel<HIPNLP_TERRAIN_SMOOTH_STEPS>, grid, block, 0, s, pa);
+            break;
+    }
+    HIP_TRY(h, hipGetLastError());
+    return HIPNLP_OK;
+}
+
+int hipnlp_pose_eval_lagrangian_grad_device(hipnlp_pose_handle* h, const double* x_dev, const double* obj_factor_dev, const double* lambda_dev,
+                                            double* out_dev, void* stream) {
+    if (!h || !x_dev || !obj_factor_dev || !lambda_dev || !out_dev) return HIPNLP_E_INVALID;
+    return pose_product_launch(h, POSE_PROD_LGRAD, x_dev, obj_factor_dev, lambda_dev, nullptr, out_dev, nullptr, stream);
+}
+
+int hipnlp_pose_eval_jac_vec_device(hipnlp_pose_handle* h, const double* x_dev, const double* v_dev, double* gradf_dot_v_dev, double* jac_v_dev, void* stream) {
+    if (!h || !x_dev || !v_dev || (!gradf_dot_v_dev && !jac_v_dev)) return HIPNLP_E_INVALID;
+    return pose_product_launch(h, POSE_PROD_JVP, x_dev, nullptr, nullptr, v_dev, jac_v_dev, gradf_dot_v_dev, stream);
+}
+
+int hipnlp_pose_eval_hess_vec_device(hipnlp_pose_handle* h, const double* x_dev, const double* obj_factor_dev, const double* lambda_dev,
+                                     const double* v_dev, double* out_dev, void* stream) {
+    if (!h || !x_dev || !obj_factor_dev || !lambda_dev || !v_dev || !out_dev) return HIPNLP_E_INVALID;
+    return pose_product_launch(h, POSE_PROD_HVP, x_dev, obj_factor_dev, lambda_dev, v_dev, out_dev, nullptr, stream);
 }
 
 int hipnlp_pose_cost_terms(hipnlp_pose_handle* h, double* values) {

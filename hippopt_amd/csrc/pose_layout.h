@@ -1,8 +1,11 @@
 // pose_layout.h — host-side structure of the static pose finder NLP: row directory in the reference's subject_to order
 // (turnkey_planners/humanoid_pose_finder/planner.py:360-399), native slot -> row / CCS position tables, bounds, parameters.
 #pragma once
+#include <cstring>
+
 #include "layout.h"
 #include "pose_hess_body.h"
+#include "pose_products.h"
 
 namespace hipnlp {
 
@@ -25,6 +28,12 @@ struct PoseLayout {
     int hnnz = 0;
     std::vector<int32_t> hperm;      // CCS position -> native Hessian slot
     std::vector<int32_t> hrow, hcol;
+    // directories of the workgroup-local products (pose_products.h): the entries of jac g by column (the CCS order itself) and by row, the
+    // touches of the Hessian's lower triangle by variable
+    std::vector<int32_t> jcolptr;            // [POSE_NX + 1] over the CCS positions
+    std::vector<int32_t> jrowptr, jrowent;   // [m + 1], [nnz]: the CCS positions of the entries of row i, in ascending column
+    std::vector<int32_t> htouchptr;          // [POSE_NX + 1] over htouch
+    std::vector<HvpTouch> htouch;            // touches of variable i in CCS-position order: (position, native slot, other variable); a diagonal entry once
     std::string error;
 
     static std::string point_name(int c) { return std::string("state.contact_points.") + (c < 4 ? "left[" : "right[") + std::to_string(c % 4) + "]"; }
@@ -162,7 +171,61 @@ struct PoseLayout {
         std::vector<int> seen(size_t(m), 0);
         for (int slot = 0; slot < gs::COUNT; ++slot) if (g_row[size_t(slot)] >= 0) seen[size_t(g_row[size_t(slot)])]++;
         for (int r = 0; r < m; ++r) if (seen[size_t(r)] != 1) { error = "internal: row " + std::to_string(r) + " not produced exactly once"; return false; }
+        return build_product_tables();
+    }
+
+    // the directories of pose_products.h from the two patterns, checked against what the device kernels stage: a pattern that does not fit
+    // is an error of the handle, nothing is truncated
+    bool build_product_tables() {
+        jcolptr.assign(size_t(POSE_NX) + 1, 0);
+        for (int e = 0; e < nnz; ++e) jcolptr[size_t(jcol[size_t(e)]) + 1]++;
+        for (int c = 0; c < POSE_NX; ++c) jcolptr[size_t(c) + 1] += jcolptr[size_t(c)];
+        jrowptr.assign(size_t(m) + 1, 0);
+        for (int e = 0; e < nnz; ++e) jrowptr[size_t(irow[size_t(e)]) + 1]++;
+        for (int r = 0; r < m; ++r) jrowptr[size_t(r) + 1] += jrowptr[size_t(r)];
+        jrowent.assign(size_t(nnz), 0);
+        {
+            std::vector<int32_t> fill(jrowptr.begin(), jrowptr.end() - 1);
+            for (int e = 0; e < nnz; ++e) jrowent[size_t(fill[size_t(irow[size_t(e)])]++)] = e;   // (e ascends by column: so does every row's list)
+        }
+        htouch.clear();
+        htouchptr.assign(size_t(POSE_NX) + 1, 0);
+        for (int i = 0; i < POSE_NX; ++i) {
+            for (int e = 0; e < hnnz; ++e) {
+                if (hrow[size_t(e)] == i) htouch.push_back({e, hperm[size_t(e)], hcol[size_t(e)]});
+                else if (hcol[size_t(e)] == i) htouch.push_back({e, hperm[size_t(e)], hrow[size_t(e)]});
+            }
+            htouchptr[size_t(i) + 1] = int32_t(htouch.size());
+        }
+        auto too_many = [&](const char* what, long have, long cap) {
+            error = std::string("the pose pattern has ") + std::to_string(have) + " " + what + ": more than the product kernels stage (" + std::to_string(cap) + ")";
+            return false;
+        };
+        if (nnz > PP_ENT_CAP) return too_many("entries of jac g", nnz, PP_ENT_CAP);
+        if (m > PP_ROW_CAP) return too_many("rows of g", m, PP_ROW_CAP);
+        if (long(htouch.size()) > PP_TOUCH_CAP) return too_many("touches of the Hessian", long(htouch.size()), PP_TOUCH_CAP);
+        for (int c = 0; c < POSE_NX; ++c) {
+            if (jcolptr[size_t(c) + 1] - jcolptr[size_t(c)] > PP_CNT_MAX) return too_many("entries in one column of jac g", jcolptr[size_t(c) + 1] - jcolptr[size_t(c)], PP_CNT_MAX);
+            if (htouchptr[size_t(c) + 1] - htouchptr[size_t(c)] > PP_CNT_MAX) return too_many("touches of one variable", htouchptr[size_t(c) + 1] - htouchptr[size_t(c)], PP_CNT_MAX);
+        }
+        for (int r = 0; r < m; ++r)
+            if (jrowptr[size_t(r) + 1] - jrowptr[size_t(r)] > PP_CNT_MAX) return too_many("entries in one row of jac g", jrowptr[size_t(r) + 1] - jrowptr[size_t(r)], PP_CNT_MAX);
+        for (int e = 0; e < nnz; ++e)
+            if (!pjs::kept(jperm[size_t(e)])) { error = "internal: a Jacobian slot of the pose pattern outside the staged pieces (pose_body.h pjs)"; return false; }
         return true;
+    }
+
+    // the device tables of the product kernels (words and directory words: pose_products.h)
+    void fill_product_tables(PoseProdTables& t) const {
+        std::memset(&t, 0, sizeof(t));
+        for (int e = 0; e < nnz; ++e) t.col_word[e] = pp_word(pjs::index(jperm[size_t(e)]), irow[size_t(e)]);
+        for (int q = 0; q < nnz; ++q) { const size_t e = size_t(jrowent[size_t(q)]); t.row_word[q] = pp_word(pjs::index(jperm[e]), jcol[e]); }
+        for (size_t q = 0; q < htouch.size(); ++q) t.touch_word[q] = pp_word(htouch[q].slot, htouch[q].other);
+        for (int c = 0; c < POSE_NX; ++c) {
+            t.col_dir[c] = pp_word(jcolptr[size_t(c)], jcolptr[size_t(c) + 1] - jcolptr[size_t(c)]);
+            t.var_dir[c] = pp_word(htouchptr[size_t(c)], htouchptr[size_t(c) + 1] - htouchptr[size_t(c)]);
+        }
+        for (int r = 0; r < m; ++r) t.row_dir[r] = pp_word(jrowptr[size_t(r)], jrowptr[size_t(r) + 1] - jrowptr[size_t(r)]);
     }
 
     // canonical bounds (CasADi Opti canon form) of one pose from its parameter vector

@@ -35,6 +35,7 @@ EXPORTS = [
     "hipnlp_pose_bounds", "hipnlp_pose_sparsity", "hipnlp_pose_eval", "hipnlp_pose_eval_device", "hipnlp_pose_cost_terms",
     "hipnlp_pose_cost_term_name", "hipnlp_pose_num_row_blocks", "hipnlp_pose_row_block", "hipnlp_pose_last_kernel_ms", "hipnlp_pose_set_host_timing",
     "hipnlp_pose_hess_nnz", "hipnlp_pose_hess_sparsity", "hipnlp_pose_eval_hess", "hipnlp_pose_eval_hess_device",
+    "hipnlp_pose_eval_lagrangian_grad_device", "hipnlp_pose_eval_jac_vec_device", "hipnlp_pose_eval_hess_vec_device",
     # include/hipnlp_ipopt.h: IPOPT's C callback quartet (+ eval_h) on top of the functions above
     "hipnlp_ipopt_eval_f", "hipnlp_ipopt_eval_grad_f", "hipnlp_ipopt_eval_g", "hipnlp_ipopt_eval_jac_g", "hipnlp_ipopt_eval_h",
     "hipnlp_ipopt_sizes", "hipnlp_ipopt_bounds", "hipnlp_ipopt_attach", "hipnlp_ipopt_detach", "hipnlp_ipopt_set_early_outputs",
@@ -171,6 +172,10 @@ def load_library(path=None):
     lib.hipnlp_pose_hess_sparsity.argtypes = [vp, ip, ip]
     lib.hipnlp_pose_eval_hess.argtypes = [vp, dp, dp, dp, dp]
     lib.hipnlp_pose_eval_hess_device.argtypes = [vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "hipnlp_pose_eval_lagrangian_grad_device"):   # (builds of earlier versions, loaded by path for comparisons, have none of the three)
+        lib.hipnlp_pose_eval_lagrangian_grad_device.argtypes = [vp, vp, vp, vp, vp, vp]
+        lib.hipnlp_pose_eval_jac_vec_device.argtypes = [vp, vp, vp, vp, vp, vp]
+        lib.hipnlp_pose_eval_hess_vec_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     lib.hipnlp_hess_nnz.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.hipnlp_hess_sparsity.argtypes = [vp, ip, ip]
     lib.hipnlp_eval_hess.argtypes = [vp, dp, dp, dp, dp]
@@ -737,6 +742,22 @@ class HipPose:
     def eval_hess_device(self, x_ptr, obj_factor_ptr, lam_ptr, hess_ptr, stream=None):
         vp = C.c_void_p
         self._check(self.lib.hipnlp_pose_eval_hess_device(self.h, vp(x_ptr), vp(obj_factor_ptr), vp(lam_ptr), vp(hess_ptr), vp(stream or None)))
+
+    # ---- products summed inside the pose's workgroup: one launch each, device pointers, asynchronous on `stream` ------------------------
+    def eval_lagrangian_grad_device(self, x_ptr, obj_factor_ptr, lam_ptr, out_ptr, stream=None):
+        """out [batch][81] = obj_factor grad f(x) + J(x)^T lam (obj_factor [batch], lam [batch][m]); jac g is never written"""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_pose_eval_lagrangian_grad_device(self.h, vp(x_ptr), vp(obj_factor_ptr or None), vp(lam_ptr or None), vp(out_ptr or None), vp(stream or None)))
+
+    def eval_jac_vec_device(self, x_ptr, v_ptr, gradf_dot_v_ptr, jac_v_ptr, stream=None):
+        """gradf_dot_v [batch] = grad f(x) . v, jac_v [batch][m] = J(x) v (v [batch][81]); either destination may be 0 / None, not both"""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_pose_eval_jac_vec_device(self.h, vp(x_ptr), vp(v_ptr or None), vp(gradf_dot_v_ptr or None), vp(jac_v_ptr or None), vp(stream or None)))
+
+    def eval_hess_vec_device(self, x_ptr, obj_factor_ptr, lam_ptr, v_ptr, out_ptr, stream=None):
+        """out [batch][81] = H(x, obj_factor, lam) v, H the Hessian of eval_hess_device; H is never written"""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_pose_eval_hess_vec_device(self.h, vp(x_ptr), vp(obj_factor_ptr or None), vp(lam_ptr or None), vp(v_ptr or None), vp(out_ptr or None), vp(stream or None)))
 
     def cost_terms(self):
         names = [self.lib.hipnlp_pose_cost_term_name(i).decode() for i in range(_abi.POSE_NCOST_TERMS)]

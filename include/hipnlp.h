@@ -724,6 +724,20 @@ int hipnlp_pose_hess_sparsity(const hipnlp_pose_handle* h, int32_t* irow, int32_
 int hipnlp_pose_eval_hess(hipnlp_pose_handle* h, const double* x, const double* obj_factor, const double* lambda, double* hess);
 int hipnlp_pose_eval_hess_device(hipnlp_pose_handle* h, const double* x_dev, const double* obj_factor_dev, const double* lambda_dev,
                                  double* hess_dev, void* stream);
+/* Products of one pose's derivatives, summed inside the pose's own workgroup from what its program holds in LDS: one kernel launch
+ * each, device pointers only, enqueued on `stream` (NULL: the handle's own stream), not synchronised, no host copy.  Neither jac g
+ * nor the Hessian is written to memory; the order of every sum is fixed (the same bits on every launch).
+ *   hipnlp_pose_eval_lagrangian_grad_device   out [batch][81] = obj_factor grad f(x) + J(x)^T lambda
+ *   hipnlp_pose_eval_jac_vec_device           gradf_dot_v [batch] = grad f(x) . v,  jac_v [batch][m] = J(x) v;  either may be NULL, not both
+ *   hipnlp_pose_eval_hess_vec_device          out [batch][81] = H(x, obj_factor, lambda) v,  H as hipnlp_pose_eval_hess_device
+ * x_dev, v_dev [batch][81], obj_factor_dev [batch], lambda_dev [batch][m].  HIPNLP_E_INVALID: a null handle or required pointer;
+ * HIPNLP_E_PARAMS: hipnlp_pose_set_params has not been called.  A non-finite result raises the pose's flag as in the calls above.  */
+int hipnlp_pose_eval_lagrangian_grad_device(hipnlp_pose_handle* h, const double* x_dev, const double* obj_factor_dev /*[batch]*/,
+                                            const double* lambda_dev /*[batch][m]*/, double* out_dev /*[batch][81]*/, void* stream);
+int hipnlp_pose_eval_jac_vec_device(hipnlp_pose_handle* h, const double* x_dev, const double* v_dev /*[batch][81]*/,
+                                    double* gradf_dot_v_dev /*[batch] or NULL*/, double* jac_v_dev /*[batch][m] or NULL*/, void* stream);
+int hipnlp_pose_eval_hess_vec_device(hipnlp_pose_handle* h, const double* x_dev, const double* obj_factor_dev, const double* lambda_dev,
+                                     const double* v_dev, double* out_dev /*[batch][81]*/, void* stream);
 int hipnlp_pose_cost_terms(hipnlp_pose_handle* h, double* values /*[batch][HIPNLP_POSE_NCOST_TERMS]*/);
 const char* hipnlp_pose_cost_term_name(int i);
 int hipnlp_pose_num_row_blocks(const hipnlp_pose_handle* h);
