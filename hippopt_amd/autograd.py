@@ -10,6 +10,12 @@
     H = nlp.hessian(x, sigma, lam)                         # the value run [B, nnz_h] (hipnlp_eval_hess_device), for many products at one x
     hv = H.matvec(v)                                       # hipnlp_hess_times_device: bit for bit the fused product
 
+    J = nlp.jacobian(x)                                    # grad f [B, n] and the value run of jac g [B, nnz] (ONE hipnlp_eval_device launch)
+    jv = J.matvec(v)                                       # J v [B, m]                 (hipnlp_jac_times_device)
+    dot, jv = J.jvp(v)                                     # grad f . v [B] and J v in one launch
+    gx = J.rmatvec(sigma, lam)                             # sigma grad f + J^T lam     (hipnlp_jac_transpose_times_device)
+    dot, jv = nlp.jacobian_vector_product(x, v)            # the two launches above (evaluate, multiply) in one call
+
 The forward pass is hipnlp_eval_device with grad f and jac g left out; the backward pass is the Lagrangian gradient
 sigma grad f + J^T lambda with sigma = df, lambda = dg (zeros for an output whose gradient is None): the Jacobian never reaches memory.
 All launches run on torch.cuda.current_stream().
@@ -17,9 +23,12 @@ All launches run on torch.cuda.current_stream().
 Second derivatives in x: the Lagrangian gradient is itself a differentiable function of x whose backward pass is the Hessian-vector
 product.  lagrangian_gradient(x, ...) with x.requires_grad, and loss.backward(create_graph=True) / torch.autograd.grad(...,
 create_graph=True) through nlp(x), record it; without create_graph the backward pass is exactly the one launch above.  The derivatives
-of the Lagrangian gradient with respect to sigma and lam are grad f . w and J w: the engine has no Jacobian-vector product, so a double
+of the Lagrangian gradient with respect to sigma and lam are grad f . w and J w.  The engine has no fused one-launch Jacobian-vector
+product for this NLP (the rows of g are not knot-local); it has the product from a stored value run of jac g.  By default a double
 backward that needs them — a loss that is not linear in f and g, e.g. (f ** 2).sum(), or a sigma / lam that requires grad — raises
-NotImplementedError instead of returning zeros.  No third derivative; no derivative with respect to the parameters.
+NotImplementedError instead of returning zeros.  KinodynamicNLP(..., jacobian_products=True) returns them through
+jacobian_vector_product (two launches: evaluate grad f and jac g into memory, multiply), so that a double backward through
+(f ** 2).sum() + (g ** 2).sum() runs.  No third derivative; no derivative with respect to the parameters.
 
 The static pose finder, a batch of B independent poses, has the same interface and is complete to second order:
 
@@ -98,6 +107,13 @@ def _lgrad_function():
             @once_differentiable
             def backward(ctx, w):
                 x, sigma, lam = ctx.saved_tensors
+                if ctx.nlp.jacobian_products:   # (opt-in: grad f . w and J w from a stored value run — evaluate, then multiply)
+                    w = w.to(torch.float64).contiguous()
+                    gx = ctx.nlp._launch_hvp(x, sigma, lam, w) if ctx.needs_input_grad[0] else None
+                    gs = gl = None
+                    if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+                        gs, gl = ctx.nlp.jacobian(x.detach())._launch(w, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+                    return gx, gs, gl, None
                 if ctx.needs_input_grad[1]:
                     raise NotImplementedError("the derivative of the Lagrangian gradient with respect to sigma is grad f . w: the engine has no "
                                               "such product (a loss that is not linear in f, or a sigma that requires grad)")
@@ -158,6 +174,48 @@ class HessianValues:
         return out
 
 
+class JacobianValues:
+    """grad f and jac g of every trajectory at one x, as the tensors `grad` [batch, n] and `values` [batch, nnz] one hipnlp_eval_device
+    launch wrote (pattern: engine.sparsity()); products with them are one launch each and run no knot program — what the inner
+    iterations of a Krylov solve on the KKT system at fixed x call."""
+
+    def __init__(self, nlp, grad, values):
+        self.nlp, self.grad, self.values = nlp, grad, values
+
+    def matvec(self, v):
+        """J v [batch, m] (hipnlp_jac_times_device)"""
+        self.nlp._check("v", v, (self.nlp.batch, self.nlp.n))
+        return self._launch(v, False, True)[1]
+
+    def grad_dot(self, v):
+        """grad f . v [batch]"""
+        self.nlp._check("v", v, (self.nlp.batch, self.nlp.n))
+        return self._launch(v, True, False)[0]
+
+    def jvp(self, v):
+        """(grad f . v [batch], J v [batch, m]) in one launch"""
+        self.nlp._check("v", v, (self.nlp.batch, self.nlp.n))
+        return self._launch(v, True, True)
+
+    def rmatvec(self, sigma, lam):
+        """sigma grad f + J^T lam [batch, n] (hipnlp_jac_transpose_times_device): sigma a number or a [batch] tensor, lam [batch, m]"""
+        nlp = self.nlp
+        sigma = nlp._sigma(sigma)
+        nlp._check("lam", lam, (nlp.batch, nlp.m))
+        out = _torch().empty_like(self.grad, memory_format=_torch().contiguous_format)
+        nlp._on_current_stream(lambda s: nlp.engine.jac_transpose_times_device(self.values.data_ptr(), lam.data_ptr(), out.data_ptr(), grad_values_ptr=self.grad.data_ptr(),
+                                                                               obj_factor_ptr=sigma.data_ptr(), stream=s))
+        return out
+
+    def _launch(self, v, want_dot, want_jv):
+        torch, nlp = _torch(), self.nlp
+        dot = torch.empty(nlp.batch, dtype=torch.float64, device=v.device) if want_dot else None
+        jv = torch.empty(nlp.batch, nlp.m, dtype=torch.float64, device=v.device) if want_jv else None
+        nlp._on_current_stream(lambda s: nlp.engine.jac_times_device(self.values.data_ptr(), v.data_ptr(), jv.data_ptr() if want_jv else 0, dot.data_ptr() if want_dot else 0,
+                                                                     grad_values_ptr=self.grad.data_ptr(), stream=s))
+        return dot, jv
+
+
 class _DeviceNLP:
     """what the two NLPs share: an engine handle on cuda:`device_index` with batch, n, m, np; tensors checked to be float64, contiguous and
     on that device; launches ordered on torch.cuda.current_stream()"""
@@ -209,14 +267,16 @@ class _DeviceNLP:
 
 class KinodynamicNLP(_DeviceNLP):
     """(f, g) = nlp(x) on a [batch, n] float64 tensor of cuda:`device`, differentiable in x.  detect_simple_bounds: the reduced NLP
-    (HIPNLP_FLAG_DETECT_SIMPLE_BOUNDS): g and lambda have the m rows of that problem."""
+    (HIPNLP_FLAG_DETECT_SIMPLE_BOUNDS): g and lambda have the m rows of that problem.  jacobian_products: the recorded Lagrangian
+    gradient's backward pass returns grad f . w for sigma and J w for lam (two launches: evaluate, multiply) instead of raising."""
 
     _recorded_lgrad = staticmethod(_lgrad_function)
 
-    def __init__(self, settings, model, batch, device=0, detect_simple_bounds=False):
+    def __init__(self, settings, model, batch, device=0, detect_simple_bounds=False, jacobian_products=False):
         self.engine = HipNlp(settings, model, batch=batch, device=device, detect_simple_bounds=detect_simple_bounds)
         self.batch, self.n, self.m, self.np = self.engine.batch, self.engine.n, self.engine.m, self.engine.np
         self.device_index = int(device)
+        self.jacobian_products = bool(jacobian_products)
 
     def __call__(self, x):
         """(f [batch], g [batch, m]); differentiable in x"""
@@ -233,7 +293,27 @@ class KinodynamicNLP(_DeviceNLP):
         self._check("lam", lam, (self.batch, self.m))
         if x.requires_grad and torch.is_grad_enabled():   # (differentiable in x: the backward pass is the Hessian-vector product)
             return _lgrad_function().apply(x, sigma, lam, self)
+        if self.jacobian_products and (sigma.requires_grad or lam.requires_grad) and torch.is_grad_enabled():
+            return _lgrad_function().apply(x, sigma, lam, self)
         return self._launch(x, sigma, lam)
+
+    def jacobian(self, x):
+        """JacobianValues at x: one hipnlp_eval_device launch with grad f and jac g into tensors; .matvec / .grad_dot / .jvp / .rmatvec
+        multiply them, one launch each.  Not recorded by autograd."""
+        torch = _torch()
+        self._check("x", x, (self.batch, self.n))
+        grad = torch.empty(self.batch, self.n, dtype=torch.float64, device=self.device)
+        values = torch.empty(self.batch, self.engine.nnz, dtype=torch.float64, device=self.device)
+        self._on_current_stream(lambda s: self.engine.eval_device(x.data_ptr(), 0, grad.data_ptr(), 0, values.data_ptr(), stream=s))
+        return JacobianValues(self, grad, values)
+
+    def jacobian_vector_product(self, x, v):
+        """(grad f(x) . v [batch], J(x) v [batch, m]) per trajectory, v [batch, n].  TWO launches — hipnlp_eval_device writes grad f and
+        jac g, hipnlp_jac_times_device multiplies them (there is no fused one-launch product for this NLP); for many products at one x
+        keep jacobian(x).  Not recorded by autograd."""
+        self._check("x", x, (self.batch, self.n))
+        self._check("v", v, (self.batch, self.n))
+        return self.jacobian(x).jvp(v)
 
     def hessian_vector_product(self, x, sigma, lam, v):
         """H(x, sigma, lam) v per trajectory ([batch, n]), H the Hessian of sigma f + lam . g in x: sigma a number or a [batch] tensor,

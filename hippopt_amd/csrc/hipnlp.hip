@@ -1253,6 +1253,171 @@ void hipnlp_knot_lgrad_kernel(LArgs a) {
 }
 
 
+// =====================================================================================================================
+// Products with a STORED value run of jac g (hipnlp_jac_times_device, hipnlp_jac_transpose_times_device; knot_jprod.h): what the inner
+// iterations of a Krylov solve on the KKT system at a fixed x call many times for one hipnlp_eval_device.  No knot program, no x, no
+// parameters, no non-finite flag: one workgroup per (trajectory, knot) brings the value runs it needs into LDS with coalesced loads and
+// sums from there, in the order of a table Layout::build wrote.
+//   J v: the ROWS of g are not knot-local, so every row has one owner knot (Layout::jp_rows) whose workgroup stages the own block, the
+//   predecessor's block, the entries of the other horizon end it needs (last knot) and the horizon-global run (knot 0), with the
+//   matching records of v; one or two rows per thread.  With a gradient run the same launch forms the knot's NXK products of
+//   grad f . v and sums them in a fixed tree into a per-knot partial; hipnlp_jac_dot_reduce_kernel adds the partials in knot order.
+//   sigma grad f + J^T lambda: the columns ARE knot-local: the own block and the multipliers of Layout::lg_rows, one column per thread —
+//   the sums of hipnlp_knot_lgrad_kernel with block positions for native slots (the tables have the shape of LgradTables).
+// =====================================================================================================================
+struct JArgs {
+    const JprodTables* jt;
+    const double* values;   // [batch][nnz]
+    const double* grad;     // [batch][n] or null
+    const double* v;        // [batch][n]
+    double* jv;             // [batch][m] or null
+    double* dot_part;       // [batch][N] or null (needs grad)
+    int32_t N, n, m, nnz_first, nnz_interior, nnz_last, nnz_glob;
+    int64_t nnz, glob_base;
+};
+__global__ __launch_bounds__(JP_WG)
+void hipnlp_jac_times_kernel(JArgs a) {
+    constexpr int WG = JP_WG;
+    __shared__ double js[JP_VALUES];
+    __shared__ double vs[JP_V_WORDS];
+    __shared__ int32_t tw[JP_ENT_CAP];
+    __shared__ double part[WG / 64];
+    static_assert(JP_BLOCK_CAP % WG == 0 && JP_OTHER_CAP <= WG && JP_GLOB_CAP <= WG && JP_V_STRIDE <= WG && JP_ROW_CAP == 2 * WG, "jprod staging by 256 threads");
+    static_assert(sizeof(double) * (JP_VALUES + JP_V_WORDS + WG / 64) + sizeof(int32_t) * JP_ENT_CAP <= 160 * 1024 / 3, "three workgroups per CU");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.y, k = blockIdx.x, N = a.N;
+    const int first = k == 0, last = k == N - 1;
+    const int pv = first ? PV_FIRST : (last ? PV_LAST : (k == 1 ? PV_SECOND : PV_INTERIOR));
+    const JprodTables& jt = *a.jt;
+    const double* vals = a.values + int64_t(b) * a.nnz;
+    const double* vb = a.v + int64_t(b) * a.n;
+    auto block_len = [&](int kk) __attribute__((always_inline)) { return kk == 0 ? a.nnz_first : (kk == N - 1 ? a.nnz_last : a.nnz_interior); };
+    auto block_base = [&](int kk) __attribute__((always_inline)) { return kk == 0 ? int64_t(0) : int64_t(a.nnz_first) + int64_t(kk - 1) * a.nnz_interior; };
+    const double gk = (a.dot_part && tid < NXK) ? a.grad[int64_t(b) * a.n + int64_t(NXK) * k + tid] : 0.0;
+    // the records of v: own knot, predecessor, other horizon end (last knot), the globals
+    if (tid < JP_V_STRIDE) {
+        const bool on = tid < NXK;
+        vs[tid] = on ? vb[int64_t(NXK) * k + tid] : 0.0;
+        vs[JP_V_PRED + tid] = (on && !first) ? vb[int64_t(NXK) * (k - 1) + tid] : 0.0;
+        vs[JP_V_OTHER + tid] = (on && last) ? vb[tid] : 0.0;
+    } else if (tid - JP_V_STRIDE < JP_V_WORDS - JP_V_GLOB) {
+        const int i = tid - JP_V_STRIDE;
+        vs[JP_V_GLOB + i] = i < NXG ? vb[int64_t(NXK) * N + i] : 0.0;
+    }
+    if (a.jv) {
+        constexpr int JB = JP_BLOCK_CAP / WG;
+        const int n_own = block_len(k), n_pred = first ? 0 : block_len(k - 1);
+        const double* own = vals + block_base(k);
+        const double* pred = vals + block_base(first ? 0 : k - 1);
+        double o[JB], p[JB];
+        int32_t wr[JP_WORDS_PER_THREAD];
+#pragma unroll
+        for (int it = 0; it < JB; ++it) { const int i = tid + it * WG; o[it] = i < n_own ? own[i] : 0.0; }
+#pragma unroll
+        for (int it = 0; it < JB; ++it) { const int i = tid + it * WG; p[it] = i < n_pred ? pred[i] : 0.0; }
+#pragma unroll
+        for (int it = 0; it < JP_WORDS_PER_THREAD; ++it) wr[it] = jt.word[pv][tid + it * WG];
+        double ex = 0.0;   // the entries of knot 0's block a last knot needs (threads 0 ..), the horizon-global run at knot 0 (threads 128 ..)
+        if (tid < JP_OTHER_CAP) {
+            const int32_t q = jt.other[tid];
+            if (last && q >= 0 && q < a.nnz_first) ex = vals[q];
+        } else if (tid - JP_OTHER_CAP < JP_GLOB_CAP) {
+            const int i = tid - JP_OTHER_CAP;
+            if (first && i < a.nnz_glob) ex = vals[a.glob_base + i];
+        }
+#pragma unroll
+        for (int it = 0; it < JB; ++it) { js[tid + it * WG] = o[it]; js[JP_POS_PRED + tid + it * WG] = p[it]; }
+#pragma unroll
+        for (int it = 0; it < JP_WORDS_PER_THREAD; ++it) tw[tid + it * WG] = wr[it];
+        if (tid < JP_OTHER_CAP + JP_GLOB_CAP) js[JP_POS_OTHER + tid] = ex;   // (JP_POS_GLOB == JP_POS_OTHER + JP_OTHER_CAP)
+    }
+    __syncthreads();
+    if (a.jv) {
+        double* out = a.jv + int64_t(b) * a.m;
+#pragma unroll
+        for (int it = 0; it < JP_ROW_CAP / WG; ++it) {
+            const int q = tid + it * WG;
+            const int32_t ra = jt.row_a[pv][q], rb = jt.row_b[pv][q], dir = jt.rdir[pv][q];
+            if (ra != G_NONE) out[ra + rb * k] = jprod_row_staged(dir, tw, js, vs);
+        }
+    }
+    if (a.dot_part) {
+        // grad f . v of this knot: one product per thread, a butterfly over the lanes, then the waves in order (knot_jprod.h jprod_dot_tree)
+        double acc = tid < NXK ? jprod_dot_product(gk, vs[tid]) : 0.0;
+#pragma unroll
+        for (int s = 1; s < 64; s <<= 1) acc += __shfl_xor(acc, s, 64);
+        if (lane == 0) part[wave] = acc;
+        __syncthreads();
+        if (tid == 0) a.dot_part[int64_t(b) * N + k] = ((part[0] + part[1]) + part[2]) + part[3];
+    }
+}
+static_assert(JP_POS_GLOB == JP_POS_OTHER + JP_OTHER_CAP && JP_WG / 64 == 4, "hipnlp_jac_times_kernel: the extra runs are staged side by side; four waves");
+// dot[b] = the per-knot partials of trajectory b in ascending knot order, from +0.0: one thread per trajectory
+__global__ __launch_bounds__(64) void hipnlp_jac_dot_reduce_kernel(const double* part, int N, int batch, double* dot) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= batch) return;
+    const double* p = part + int64_t(b) * N;
+    double acc = 0.0;
+    for (int k = 0; k < N; ++k) acc += p[k];
+    dot[b] = acc;
+}
+
+struct JTArgs {
+    const LgradTables* tt;   // (the shape of the fused kernel's tables: block positions in place of native slots)
+    const double* values;   // [batch][nnz]
+    const double* grad;     // [batch][n] or null
+    const double* sigma;    // [batch] or null with grad null
+    const double* lambda;   // [batch][m]
+    double* out;            // [batch][n]
+    int32_t N, n, m, nnz_first, nnz_interior, nnz_last, nnz_glob;
+    int64_t nnz, glob_base;
+};
+__global__ __launch_bounds__(256)
+void hipnlp_jac_transpose_times_kernel(JTArgs a) {
+    constexpr int WG = 256, JB = LG_ENT_CAP / WG, LQ = LG_LAM_CAP / WG;
+    __shared__ double js[LG_ENT_CAP + 16];
+    __shared__ double ls[LG_LAM_CAP];
+    __shared__ int32_t lw[LG_ENT_CAP + 16];
+    const int tid = threadIdx.x;
+    const int b = blockIdx.y, k = blockIdx.x, N = a.N;
+    const int first = k == 0, last = k == N - 1;
+    const int v = first ? VAR_FIRST : (last ? VAR_LAST : VAR_INTERIOR);
+    const LgradTables& lt = *a.tt;
+    const double* vals = a.values + int64_t(b) * a.nnz;
+    const double* own = vals + (first ? int64_t(0) : int64_t(a.nnz_first) + int64_t(k - 1) * a.nnz_interior);
+    const double* lam = a.lambda + int64_t(b) * a.m;
+    const int n_own = first ? a.nnz_first : (last ? a.nnz_last : a.nnz_interior);
+    double o[JB], lv[LQ];
+    int32_t w[JB];
+#pragma unroll
+    for (int it = 0; it < JB; ++it) { const int i = tid + it * WG; o[it] = i < n_own ? own[i] : 0.0; }
+#pragma unroll
+    for (int it = 0; it < LQ; ++it) {
+        const int32_t ra = lt.row_a[v][tid + it * WG], rb = lt.row_b[v][tid + it * WG];
+        lv[it] = ra != G_NONE ? lam[ra + rb * k] : 0.0;
+    }
+#pragma unroll
+    for (int it = 0; it < JB; ++it) w[it] = lt.word[v][tid + it * WG];
+    const int32_t wg = lt.word[v][LG_ENT_CAP + (tid & 15)];
+    const int32_t e0 = lt.beg[v][tid], e1 = lt.end[v][tid];
+    const double og = (last && tid < 16 && tid < a.nnz_glob) ? vals[a.glob_base + tid] : 0.0;
+    const bool with_grad = a.grad != nullptr;
+    const double sig = with_grad ? a.sigma[b] : 0.0;
+    const double gc = (with_grad && tid < NXK) ? a.grad[int64_t(b) * a.n + int64_t(NXK) * k + tid] : 0.0;
+#pragma unroll
+    for (int it = 0; it < JB; ++it) { js[tid + it * WG] = o[it]; lw[tid + it * WG] = w[it]; }
+#pragma unroll
+    for (int it = 0; it < LQ; ++it) ls[tid + it * WG] = lv[it];
+    if (tid < 16) { js[LG_ENT_CAP + tid] = og; lw[LG_ENT_CAP + tid] = wg; }
+    __syncthreads();
+    if (tid < NXK) {
+        a.out[int64_t(b) * a.n + int64_t(NXK) * k + tid] = jprod_column_staged(with_grad, sig, gc, e0, e1, lw, ls, js);
+    } else if (last && tid >= LG_SPAN_GLOB && tid < LG_SPAN_GLOB + NXG) {   // the global variables carry no cost
+        a.out[int64_t(b) * a.n + int64_t(NXK) * N + (tid - LG_SPAN_GLOB)] = jprod_column_staged(with_grad, sig, 0.0, e0, e1, lw, ls, js);
+    }
+}
+
+
 // Throughput variant only (4 waves; the latency variant sums inside the knot kernel, see pub_step): f[b] = sum over knots and
 // terms, cost_terms[b][t] = sum over knots.  One workgroup per trajectory.  Thread (group g = tid / 16, column c = tid % 16) sums
 // column c of the knots g, g + 16, ...: all its loads are independent and issued together (ONE memory round trip), then a fixed
@@ -1514,6 +1679,11 @@ struct hipnlp_handle {
     int32_t hseq = 0;   // Hessian launches so far (generation of d_hflag)
     LgradTables* d_lt = nullptr;   // Lagrangian gradient (hipnlp_eval_lagrangian_grad_device): its tables, uploaded at the first call
     HvpTables* d_vt = nullptr;     // Hessian-vector product (hipnlp_eval_hess_vec_device, hipnlp_hess_times_device): its tables, uploaded at the first call
+    // products with a stored value run of jac g (hipnlp_jac_times_device, hipnlp_jac_transpose_times_device): tables uploaded at the first
+    // call, and the per-knot partials [batch][N] of grad f . v
+    JprodTables* d_jt = nullptr;
+    LgradTables* d_jtt = nullptr;
+    double* d_jdot = nullptr;
     std::string err;
 };
 
@@ -1568,7 +1738,7 @@ static void free_all(hipnlp_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->dev);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* dptrs[] = {h->d_tb, h->d_ctpl, h->d_ctpl_of_b, h->d_healed, h->d_x, h->d_pk, h->d_cost_knot, h->d_gp, h->d_cost_pub, h->d_out, h->d_ht, h->d_sigma, h->d_hess, h->d_hflag, h->d_htrash, h->d_lt, h->d_vt};
+    void* dptrs[] = {h->d_tb, h->d_ctpl, h->d_ctpl_of_b, h->d_healed, h->d_x, h->d_pk, h->d_cost_knot, h->d_gp, h->d_cost_pub, h->d_out, h->d_ht, h->d_sigma, h->d_hess, h->d_hflag, h->d_htrash, h->d_lt, h->d_vt, h->d_jt, h->d_jtt, h->d_jdot};
     for (void* q : dptrs) if (q) (void)hipFree(q);
     void* hptrs[] = {h->h_x, h->h_out, h->h_hess, h->h_hflag, h->h_sl};
     for (void* q : hptrs) if (q) (void)hipHostFree(q);
@@ -2852,6 +3022,80 @@ int hipnlp_hess_times_device(hipnlp_handle* h, const double* values_dev, const d
     a.vt = h->d_vt; a.values = values_dev; a.v = v_dev; a.out = out_dev;
     a.N = h->L.N; a.n = h->L.n; a.nnz_knot = h->HL.nnz_knot; a.n_couple = h->HL.n_couple; a.nnz_h = hess_count(h);
     hipLaunchKernelGGL(hipnlp_hess_times_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(256), 0, stream ? hipStream_t(stream) : h->stream, a);
+    HIP_TRY(h, hipGetLastError());
+    return HIPNLP_OK;
+}
+// ---- products with a stored value run of jac g (include/hipnlp.h) -----------------------------------------------------------------------
+static int jprod_prepare(hipnlp_handle* h, const char* who) {
+    const Layout& L = h->L;
+    if (!L.jprod_ok) { h->err = std::string(who) + ": " + L.jprod_error; return HIPNLP_E_UNSUPPORTED; }
+    if (!h->d_jt) {
+        JprodTables* t = new JprodTables();
+        L.fill_jprod_tables(*t);
+        const int rc = upload_table(h, reinterpret_cast<void**>(&h->d_jt), t, sizeof(JprodTables), "Jacobian-vector tables");
+        delete t;
+        if (rc != HIPNLP_OK) return rc;
+    }
+    if (!h->d_jtt) {   // the column directory: LgradTables with the position in the knot block (horizon-global run: behind LG_ENT_CAP) for the native slot
+        LgradTables* t = new LgradTables();
+        std::memset(t, 0, sizeof(LgradTables));
+        for (int v = 0; v < 3; ++v) {
+            for (int i = 0; i < LG_ENT_CAP + 16; ++i) t->word[v][i] = -1;
+            for (size_t i = 0; i < L.lg_ent[v].size(); ++i) t->word[v][i] = int32_t(L.jt_pos[v][i] | (L.lg_ent[v][i].lam << LG_SLOT_BITS));
+            for (int c = 0; c < NXK && !L.lg_cbeg[v].empty(); ++c) { t->beg[v][c] = L.lg_cbeg[v][size_t(c)]; t->end[v][c] = L.lg_cbeg[v][size_t(c) + 1]; }
+            for (int q = 0; q < LG_LAM_CAP; ++q) {
+                const bool on = q < int(L.lg_rows[v].size());
+                t->row_a[v][q] = on ? L.lg_rows[v][size_t(q)].first : G_NONE;
+                t->row_b[v][q] = on ? L.lg_rows[v][size_t(q)].second : 0;
+            }
+        }
+        static_assert(JP_GLOB_CAP <= 16 && LG_ENT_CAP + 16 <= (1 << LG_SLOT_BITS), "horizon-global entry words");
+        for (size_t i = 0; i < L.lg_glob.size(); ++i) t->word[VAR_LAST][LG_ENT_CAP + i] = int32_t((LG_ENT_CAP + L.jt_gpos[i]) | (L.lg_glob[i].lam << LG_SLOT_BITS));
+        for (int c = 0; c < NXG; ++c) { t->beg[VAR_LAST][LG_SPAN_GLOB + c] = LG_ENT_CAP + L.lg_gcbeg[size_t(c)]; t->end[VAR_LAST][LG_SPAN_GLOB + c] = LG_ENT_CAP + L.lg_gcbeg[size_t(c) + 1]; }
+        const int rc = upload_table(h, reinterpret_cast<void**>(&h->d_jtt), t, sizeof(LgradTables), "Jacobian-transpose tables");
+        delete t;
+        if (rc != HIPNLP_OK) return rc;
+    }
+    return HIPNLP_OK;
+}
+int hipnlp_jac_times_device(hipnlp_handle* h, const double* jac_values_dev, const double* grad_values_dev, const double* v_dev, double* jv_dev, double* dot_dev, void* stream) {
+    if (!h || !jac_values_dev || !v_dev || (!jv_dev && !dot_dev) || (dot_dev && !grad_values_dev)) return HIPNLP_E_INVALID;
+    NOT_FRONT(h, "hipnlp_jac_times_device");
+    if (const int rc = whole_horizon_only(h, "hipnlp_jac_times_device", "a row of g has entries in the blocks of two knots")) return rc;
+    const int rc = jprod_prepare(h, "hipnlp_jac_times_device");
+    if (rc != HIPNLP_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->dev));
+    if (dot_dev && !h->d_jdot) HIP_TRY(h, hipMalloc(&h->d_jdot, size_t(h->batch) * size_t(h->L.N) * sizeof(double)));
+    hipStream_t s = stream ? hipStream_t(stream) : h->stream;
+    const Layout& L = h->L;
+    JArgs a;
+    a.jt = h->d_jt; a.values = jac_values_dev; a.grad = dot_dev ? grad_values_dev : nullptr; a.v = v_dev; a.jv = jv_dev; a.dot_part = dot_dev ? h->d_jdot : nullptr;
+    a.N = L.N; a.n = L.n; a.m = L.m;
+    a.nnz_first = L.nnz_v[VAR_FIRST]; a.nnz_interior = L.nnz_v[VAR_INTERIOR]; a.nnz_last = L.nnz_v[VAR_LAST]; a.nnz_glob = int32_t(L.jperm_glob.size());
+    a.nnz = L.nnz; a.glob_base = L.jac_glob_base;
+    hipLaunchKernelGGL(hipnlp_jac_times_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(JP_WG), 0, s, a);
+    HIP_TRY(h, hipGetLastError());
+    if (dot_dev) {
+        hipLaunchKernelGGL(hipnlp_jac_dot_reduce_kernel, dim3(unsigned((h->batch + 63) / 64)), dim3(64), 0, s, (const double*)h->d_jdot, L.N, h->batch, dot_dev);
+        HIP_TRY(h, hipGetLastError());
+    }
+    return HIPNLP_OK;
+}
+int hipnlp_jac_transpose_times_device(hipnlp_handle* h, const double* jac_values_dev, const double* grad_values_dev, const double* obj_factor_dev, const double* lambda_dev,
+                                      double* out_dev, void* stream) {
+    if (!h || !jac_values_dev || !lambda_dev || !out_dev || (grad_values_dev && !obj_factor_dev)) return HIPNLP_E_INVALID;
+    NOT_FRONT(h, "hipnlp_jac_transpose_times_device");
+    if (const int rc = whole_horizon_only(h, "hipnlp_jac_transpose_times_device", "the product needs every knot")) return rc;
+    const int rc = jprod_prepare(h, "hipnlp_jac_transpose_times_device");
+    if (rc != HIPNLP_OK) return rc;
+    HIP_TRY(h, hipSetDevice(h->dev));
+    const Layout& L = h->L;
+    JTArgs a;
+    a.tt = h->d_jtt; a.values = jac_values_dev; a.grad = grad_values_dev; a.sigma = obj_factor_dev; a.lambda = lambda_dev; a.out = out_dev;
+    a.N = L.N; a.n = L.n; a.m = L.m;
+    a.nnz_first = L.nnz_v[VAR_FIRST]; a.nnz_interior = L.nnz_v[VAR_INTERIOR]; a.nnz_last = L.nnz_v[VAR_LAST]; a.nnz_glob = int32_t(L.jperm_glob.size());
+    a.nnz = L.nnz; a.glob_base = L.jac_glob_base;
+    hipLaunchKernelGGL(hipnlp_jac_transpose_times_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(256), 0, stream ? hipStream_t(stream) : h->stream, a);
     HIP_TRY(h, hipGetLastError());
     return HIPNLP_OK;
 }

@@ -8,12 +8,14 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <limits>
 #include <string>
 #include <utility>
 #include <vector>
 
 #include "knot_body.h"
+#include "knot_jprod.h"
 #include "knot_lgrad.h"
 
 namespace hipnlp {
@@ -152,6 +154,21 @@ struct Layout {
     std::vector<std::pair<int32_t, int32_t>> lg_rows[3];
     bool lgrad_ok = false;
     std::string lgrad_error;
+    // Products with a stored value run of jac g (knot_jprod.h, hipnlp_jac_times_device / hipnlp_jac_transpose_times_device).
+    // Row directory: every row of g has ONE owner knot — the knot of its row block (a knot's own rows and its trapezoid-defect rows; the
+    // x_0 rows: knot 0; final-state and periodicity rows: knot N - 1).  Per pair variant (own block, predecessor's block) jp_rows lists
+    // the owned rows {row_a, row_b}, jp_rbeg[pv][q] .. jp_rbeg[pv][q + 1] the entries of owned row q in ascending global column, each the
+    // staged value (own block, predecessor's block, jp_other: the positions in knot 0's block the last knot stages, the horizon-global
+    // run) and the staged element of v.  Built from irow / jcol at a representative knot and then CHECKED against the pattern at every knot.
+    // Column directory: jt_pos[v][e] / jt_gpos[e] the position in the value run of the entry lg_ent[v][e] / lg_glob[e].
+    // jprod_ok: the tables fit what the device kernels stage (else jprod_error).
+    std::vector<JprodEntry> jp_ent[PV_COUNT];
+    std::vector<int32_t> jp_rbeg[PV_COUNT];
+    std::vector<std::pair<int32_t, int32_t>> jp_rows[PV_COUNT];
+    std::vector<int32_t> jp_other;
+    std::vector<int32_t> jt_pos[3], jt_gpos;
+    bool jprod_ok = false;
+    std::string jprod_error;
     std::vector<int32_t> irow, jcol;      // full pattern, CCS order
     std::string error;
 
@@ -160,6 +177,7 @@ struct Layout {
     }
     int variant_of(int k) const { return k == 0 ? VAR_FIRST : (k == N - 1 ? VAR_LAST : VAR_INTERIOR); }
     long jac_base(int k) const { return k == 0 ? 0 : long(nnz_v[VAR_FIRST]) + long(k - 1) * nnz_v[VAR_INTERIOR]; }
+    int pair_variant_of(int k) const { return k == 0 ? PV_FIRST : (k == N - 1 ? PV_LAST : (k == 1 ? PV_SECOND : PV_INTERIOR)); }
 
     int add(const std::string& name, int rows, int k0, int nk) {
         RowBlock b{name, m_full, rows, k0, nk};
@@ -429,7 +447,151 @@ struct Layout {
         if (int(irow.size()) != nnz) { error = "internal: nnz mismatch"; return false; }
         nconst_total = int(jperm_glob.size());
         for (int k = 0; k < N; ++k) nconst_total += nnz_v[variant_of(k)] - nvary_v[variant_of(k)];
+        build_jprod();
         return true;
+    }
+
+    // the rows knot k owns, in ascending row: {row, stride in k}
+    std::vector<std::pair<int32_t, int32_t>> owned_rows(int k) const {
+        std::vector<std::pair<int32_t, int32_t>> out;
+        for (const RowBlock& b : blocks) {
+            if (k < b.k0 || k >= b.k0 + b.nk) continue;
+            const int stride = b.nk > 1 ? (lifted ? b.kept : b.rows) : 0;
+            for (int i = 0; i < b.rows; ++i) {
+                const int r = row_of(b, k - b.k0, i);
+                if (r >= 0) out.push_back({r, stride});
+            }
+        }
+        std::sort(out.begin(), out.end());
+        return out;
+    }
+    // directories of the stored-values products (knot_jprod.h); sets jprod_ok / jprod_error
+    void build_jprod() {
+        jprod_ok = false;
+        jprod_error.clear();
+        jp_other.clear();
+        jt_gpos.clear();
+        for (int pv = 0; pv < PV_COUNT; ++pv) { jp_ent[pv].clear(); jp_rbeg[pv].clear(); jp_rows[pv].clear(); }
+        auto fail = [&](const std::string& what) { jprod_error = what; };
+        // ---- column directory: the (column, row) order of lg_ent with native slots replaced by positions in the block ----
+        for (int v = 0; v < 3; ++v) {
+            jt_pos[v].clear();
+            std::vector<int32_t> inv(js::COUNT, -1);
+            for (size_t i = 0; i < jperm[v].size(); ++i) inv[size_t(jperm[v][i])] = int32_t(i);
+            for (const LgradEntry& e : lg_ent[v]) {
+                if (inv[size_t(e.slot)] < 0) return fail("internal: an entry of the Lagrangian-gradient tables is not in the knot block");
+                jt_pos[v].push_back(inv[size_t(e.slot)]);
+            }
+        }
+        for (const LgradEntry& e : lg_glob) {
+            int q = 0;
+            while (q < int(jperm_glob.size()) && jperm_glob[size_t(q)] != e.slot) ++q;
+            if (q == int(jperm_glob.size())) return fail("internal: a horizon-global entry is not in the global run");
+            jt_gpos.push_back(q);
+        }
+        // ---- row directory ----
+        // entries of the pattern by row, each row in ascending global column
+        std::vector<int32_t> rptr(size_t(m) + 1, 0), ridx(static_cast<size_t>(nnz));
+        for (int p = 0; p < nnz; ++p) {
+            if (irow[size_t(p)] < 0 || irow[size_t(p)] >= m) return fail("internal: a pattern entry has no row");
+            rptr[size_t(irow[size_t(p)]) + 1]++;
+        }
+        for (int r = 0; r < m; ++r) rptr[size_t(r) + 1] += rptr[size_t(r)];
+        {
+            std::vector<int32_t> at(rptr.begin(), rptr.end() - 1);
+            for (int p = 0; p < nnz; ++p) ridx[size_t(at[size_t(irow[size_t(p)])]++)] = p;
+            for (int r = 0; r < m; ++r)
+                std::sort(ridx.begin() + rptr[size_t(r)], ridx.begin() + rptr[size_t(r) + 1], [&](int32_t a, int32_t b) { return jcol[size_t(a)] < jcol[size_t(b)]; });
+        }
+        // entry p of the pattern as knot k's workgroup stages it; other: the list of knot-0 positions (appended to when grow)
+        auto staged = [&](int p, int k, std::vector<int32_t>& other, bool grow, JprodEntry* out) {
+            if (p >= jac_glob_base) {
+                if (k != 0) return false;
+                *out = {JP_POS_GLOB + (p - jac_glob_base), JP_V_GLOB + (jcol[size_t(p)] - NXK * N)};
+                return true;
+            }
+            const int kc = jcol[size_t(p)] / NXK, var = jcol[size_t(p)] % NXK, pos = p - int(jac_base(kc));
+            if (kc == k) { *out = {pos, var}; return true; }
+            if (kc == k - 1) { *out = {JP_POS_PRED + pos, JP_V_PRED + var}; return true; }
+            if (k == N - 1 && kc == 0) {
+                size_t q = 0;
+                while (q < other.size() && other[q] != pos) ++q;
+                if (q == other.size()) { if (!grow) return false; other.push_back(pos); }
+                *out = {JP_POS_OTHER + int(q), JP_V_OTHER + var};
+                return true;
+            }
+            return false;
+        };
+        const int rep[PV_COUNT] = {0, 1, 2, N - 1};
+        for (int pv = 0; pv < PV_COUNT; ++pv) {
+            const int k = rep[pv];
+            jp_rbeg[pv].assign(1, 0);
+            if (k >= N || pair_variant_of(k) != pv) continue;
+            for (auto& rs : owned_rows(k)) {
+                jp_rows[pv].push_back({rs.first - rs.second * k, rs.second});
+                for (int q = rptr[size_t(rs.first)]; q < rptr[size_t(rs.first) + 1]; ++q) {
+                    JprodEntry e;
+                    if (!staged(ridx[size_t(q)], k, jp_other, true, &e))
+                        return fail("row " + std::to_string(rs.first) + " of knot " + std::to_string(k) + " has an entry outside the blocks its owner stages");
+                    jp_ent[pv].push_back(e);
+                }
+                jp_rbeg[pv].push_back(int32_t(jp_ent[pv].size()));
+            }
+        }
+        // the tables against the pattern at EVERY knot: every row owned once, every entry listed once and where the tables say
+        {
+            std::vector<unsigned char> seen(size_t(m), 0);
+            long entries = 0;
+            for (int k = 0; k < N; ++k) {
+                const int pv = pair_variant_of(k);
+                for (size_t q = 0; q < jp_rows[pv].size(); ++q) {
+                    const long r = long(jp_rows[pv][q].first) + long(jp_rows[pv][q].second) * k;
+                    if (r < 0 || r >= m || seen[size_t(r)]) return fail("internal: row directory: a row of knot " + std::to_string(k) + " is out of range or owned twice");
+                    seen[size_t(r)] = 1;
+                    const int beg = jp_rbeg[pv][q], end = jp_rbeg[pv][q + 1];
+                    if (end - beg != rptr[size_t(r) + 1] - rptr[size_t(r)]) return fail("internal: row directory: knot " + std::to_string(k) + " is not like its representative");
+                    for (int e = beg; e < end; ++e) {
+                        JprodEntry w;
+                        if (!staged(ridx[size_t(rptr[size_t(r)] + (e - beg))], k, jp_other, false, &w) || w.pos != jp_ent[pv][size_t(e)].pos || w.var != jp_ent[pv][size_t(e)].var)
+                            return fail("internal: row directory: knot " + std::to_string(k) + " is not like its representative");
+                    }
+                    entries += end - beg;
+                }
+            }
+            for (int r = 0; r < m; ++r) if (!seen[size_t(r)]) return fail("internal: row directory: row " + std::to_string(r) + " has no owner");
+            if (entries != nnz) return fail("internal: row directory: entries missed");
+        }
+        // ---- what the device kernels stage ----
+        for (int v = 0; v < 3; ++v)
+            if (nnz_v[v] > JP_BLOCK_CAP || int(lg_rows[v].size()) > LG_LAM_CAP)
+                return fail("a knot block of jac g has " + std::to_string(nnz_v[v]) + " entries in " + std::to_string(lg_rows[v].size()) + " rows: more than the stored-values "
+                            "products stage (" + std::to_string(JP_BLOCK_CAP) + " / " + std::to_string(LG_LAM_CAP) + ")");
+        for (int pv = 0; pv < PV_COUNT; ++pv) {
+            if (int(jp_ent[pv].size()) > JP_ENT_CAP || int(jp_rows[pv].size()) > JP_ROW_CAP)
+                return fail("a knot owns " + std::to_string(jp_rows[pv].size()) + " rows of g with " + std::to_string(jp_ent[pv].size()) + " entries: more than the stored-values "
+                            "J v stages (" + std::to_string(JP_ROW_CAP) + " / " + std::to_string(JP_ENT_CAP) + ")");
+            for (size_t q = 0; q + 1 < jp_rbeg[pv].size(); ++q)
+                if (jp_rbeg[pv][q + 1] - jp_rbeg[pv][q] > JP_CNT_MAX) return fail("a row of g has more than " + std::to_string(JP_CNT_MAX) + " entries");
+        }
+        if (int(jp_other.size()) > JP_OTHER_CAP)
+            return fail("the last knot needs " + std::to_string(jp_other.size()) + " entries of the first block: more than the stored-values J v stages (" + std::to_string(JP_OTHER_CAP) + ")");
+        if (int(jperm_glob.size()) > JP_GLOB_CAP)
+            return fail("more than " + std::to_string(JP_GLOB_CAP) + " entries in the horizon-global columns");
+        jprod_ok = true;
+    }
+    // the device tables of hipnlp_jac_times_kernel from the row directory (jprod_ok)
+    void fill_jprod_tables(JprodTables& t) const {
+        std::memset(&t, 0, sizeof(JprodTables));
+        for (int pv = 0; pv < PV_COUNT; ++pv) {
+            for (size_t e = 0; e < jp_ent[pv].size(); ++e) t.word[pv][e] = jp_word(jp_ent[pv][e].pos, jp_ent[pv][e].var);
+            for (int q = 0; q < JP_ROW_CAP; ++q) {
+                const bool on = q < int(jp_rows[pv].size());
+                t.rdir[pv][q] = on ? jp_word(jp_rbeg[pv][size_t(q)], jp_rbeg[pv][size_t(q) + 1] - jp_rbeg[pv][size_t(q)]) : 0;
+                t.row_a[pv][q] = on ? jp_rows[pv][size_t(q)].first : G_NONE;
+                t.row_b[pv][q] = on ? jp_rows[pv][size_t(q)].second : 0;
+            }
+        }
+        for (int q = 0; q < JP_OTHER_CAP; ++q) t.other[q] = q < int(jp_other.size()) ? jp_other[size_t(q)] : -1;
     }
 
     // is entry i of the pattern (0 .. nnz) constant?  (mask of the whole trajectory, in the order of irow / jcol)

@@ -28,6 +28,7 @@ EXPORTS = [
     "hipnlp_device_numa_node", "hipnlp_pin_thread_to_device_numa_node",
     "hipnlp_hess_nnz", "hipnlp_hess_sparsity", "hipnlp_eval_hess", "hipnlp_eval_hess_at", "hipnlp_set_hessian_early_run", "hipnlp_get_hessian_early_run", "hipnlp_hessian_early_run_reason", "hipnlp_eval_hess_device",
     "hipnlp_eval_lagrangian_grad_device", "hipnlp_eval_hess_vec_device", "hipnlp_hess_times_device",
+    "hipnlp_jac_times_device", "hipnlp_jac_transpose_times_device",
     "hipnlp_eval_pinned", "hipnlp_set_prefetch", "hipnlp_set_early_outputs", "hipnlp_set_host_timing", "hipnlp_host_register", "hipnlp_host_unregister",
     "hipnlp_multi_create", "hipnlp_multi_plan", "hipnlp_multi_info", "hipnlp_multi_breakdown", "hipnlp_multi_set_threads",
     "hipnlp_host_breakdown", "hipnlp_set_auto_register", "hipnlp_host_stats", "hipnlp_set_constant_jacobian", "hipnlp_forget_jac_destination", "hipnlp_jac_constant_mask", "hipnlp_host_release_auto_ranges",
@@ -216,6 +217,9 @@ def load_library(path=None):
     if hasattr(lib, "hipnlp_eval_hess_vec_device"):
         lib.hipnlp_eval_hess_vec_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         lib.hipnlp_hess_times_device.argtypes = [vp, vp, vp, vp, vp]
+    if hasattr(lib, "hipnlp_jac_times_device"):
+        lib.hipnlp_jac_times_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+        lib.hipnlp_jac_transpose_times_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     _libs[path] = lib
     return lib
 
@@ -596,6 +600,20 @@ class HipNlp:
         bit the result of eval_hess_vec_device; asynchronous on `stream`; out may not alias v"""
         vp = C.c_void_p
         self._check(self.lib.hipnlp_hess_times_device(self.h, vp(values_ptr), vp(v_ptr), vp(out_ptr), vp(stream or None)))
+
+    def jac_times_device(self, jac_values_ptr, v_ptr, jv_ptr=0, dot_ptr=0, grad_values_ptr=0, stream=0):
+        """jv [batch][m] = J v and / or dot [batch] = grad f . v from the jac run [batch][nnz] (and the grad f [batch][n]) eval_device of
+        this handle wrote (hipnlp_jac_times_device); a destination of 0 is left alone, dot needs grad_values; asynchronous on `stream`"""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_jac_times_device(self.h, vp(jac_values_ptr or None), vp(grad_values_ptr or None), vp(v_ptr or None), vp(jv_ptr or None),
+                                                     vp(dot_ptr or None), vp(stream or None)))
+
+    def jac_transpose_times_device(self, jac_values_ptr, lam_ptr, out_ptr, grad_values_ptr=0, obj_factor_ptr=0, stream=0):
+        """out [batch][n] = obj_factor grad f + J^T lam from the jac run [batch][nnz] eval_device of this handle wrote
+        (hipnlp_jac_transpose_times_device); without grad_values: J^T lam; asynchronous on `stream`"""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_jac_transpose_times_device(self.h, vp(jac_values_ptr or None), vp(grad_values_ptr or None), vp(obj_factor_ptr or None),
+                                                               vp(lam_ptr or None), vp(out_ptr or None), vp(stream or None)))
 
     def cost_terms(self):
         out = np.empty((self.batch, _abi.NCOST_TERMS))

@@ -452,6 +452,31 @@ int hipnlp_eval_hess_vec_device(hipnlp_handle* h, const double* x_dev, const dou
  * bit its result. */
 int hipnlp_hess_times_device(hipnlp_handle* h, const double* values_dev, const double* v_dev, double* out_dev, void* stream);
 
+/* Products with a STORED value run of jac g, for many products at one x (the inner iterations of a Krylov solve on the KKT system): no
+ * knot program runs, no x, no parameters, no non-finite flag.  jac_values_dev [batch][nnz] is a jac run exactly as hipnlp_eval_device
+ * of THIS handle leaves it — in its order (CCS or HIPNLP_FLAG_JAC_VARYING_FIRST), every entry valid, the constant ones included;
+ * grad_values_dev [batch][n] the grad f of the same call.  Device pointers, enqueued on `stream` (NULL = the handle's own), not
+ * synchronised; stream rules and error codes of hipnlp_hess_times_device (no HIPNLP_E_PARAMS).  Every sum runs in a fixed order from a
+ * table ("The Jacobian's rows are not knot-local"): the same bits at every position of a batch and for both jac orders.
+ *
+ * hipnlp_jac_times_device:  jv_dev [batch][m] = J v  and / or  dot_dev [batch] = grad f . v,  v_dev [batch][n].  Either output may be
+ * NULL (it is left alone), not both; dot_dev needs grad_values_dev (otherwise grad_values_dev may be NULL).  Every row of g has one
+ * owner knot whose workgroup sums it from +0.0 in ascending column, one fused multiply-add per entry; every element of jv is written
+ * exactly once.  grad f . v: the products of a knot summed in a fixed tree into a per-knot partial (a workspace of the handle: calls
+ * that ask for dot_dev on ONE handle must be ordered on one stream), the partials added in ascending knot order by a second small
+ * launch on the same stream.  The outputs may not alias the inputs.
+ *
+ * hipnlp_jac_transpose_times_device:  out_dev [batch][n] = obj_factor grad f + J^T lambda,  lambda_dev [batch][m]; with
+ * grad_values_dev NULL (obj_factor_dev may then be NULL too)  out = J^T lambda.  One column per thread in the (column, row) order of
+ * hipnlp_eval_lagrangian_grad_device, obj_factor grad f_c first (+0.0 without a gradient).
+ *
+ * Return HIPNLP_E_INVALID for a missing required pointer, HIPNLP_E_UNSUPPORTED on a multi-device handle, on a shard handle (knot_begin /
+ * knot_end not the whole horizon) and for a layout whose tables exceed what the kernels stage (hipnlp_last_error says which). */
+int hipnlp_jac_times_device(hipnlp_handle* h, const double* jac_values_dev, const double* grad_values_dev, const double* v_dev,
+                            double* jv_dev, double* dot_dev, void* stream);
+int hipnlp_jac_transpose_times_device(hipnlp_handle* h, const double* jac_values_dev, const double* grad_values_dev,
+                                      const double* obj_factor_dev, const double* lambda_dev, double* out_dev, void* stream);
+
 /* Sharded variant (multi-GPU): the handle owns knots [knot_begin, knot_end).  Outputs are
  * shard-local and contiguous so that one RCCL all-gather reassembles them:
  *   grad_shard [batch][shard_grad]  = grad f entries of the shard's knots (+ the 6 global entries on the last shard)
