@@ -551,6 +551,15 @@ void hipnlp_knot_kernel(const DeviceTables* tb_p, const double* x_p, const doubl
         asm volatile("global_store_dwordx2 %0, %1, %2 sc0 sc1" ::"v"(byte_off), "v"(v), "s"(base) : "memory");   // (system scope: written through the L2)
     };
     const bool early_on = EARLY_OUT && a.early != 0;
+    // A final store of jac g / g / grad f.  SPLIT launches write them THROUGH the L2 (sc1): their 1.7 MB of outputs leave in the launch's
+    // last microsecond, and left dirty in the L2 they are written back at the end of the kernel, behind the last workgroup — measured on the
+    // 100-knot launch 7.47 -> 7.28 us, stairs 8.55 -> 8.32 us (profiles/r10_split_packed_copy_out.txt; `sc0 sc1` is no different, `nt` is not
+    // for data the next kernel reads).  Inline assembly as store_unwaited: nothing waits for these stores.  base: uniform; the byte offset
+    // stays inside one knot block of jac g / one trajectory's g or grad f (< 2^31).  Every other instantiation: the plain store.
+    auto put = [](double* base, int idx, double v) __attribute__((always_inline)) {
+        if constexpr (SPLIT) asm volatile("global_store_dwordx2 %0, %1, %2 sc1" ::"v"(idx * 8), "v"(v), "s"(base) : "memory");
+        else base[idx] = v;
+    };
     auto early_out = [&]() __attribute__((always_inline)) {
         if (!early_on) return;
         if (a.jac) {
@@ -656,14 +665,14 @@ void hipnlp_knot_kernel(const DeviceTables* tb_p, const double* x_p, const doubl
     if (a.jac) {
         double* out = a.jac + int64_t(b) * a.jac_stride + (jbase - a.jac_off);
 #pragma unroll
-        for (int it = 0; it < JP_ITERS; ++it) if (jp[it] >= 0 && !(early_on && (jp[it] & COPY_EARLY))) out[VARY ? jp_pos(jp[it]) : tid + it * WG] = jvals[it];
+        for (int it = 0; it < JP_ITERS; ++it) if (jp[it] >= 0 && !(early_on && (jp[it] & COPY_EARLY))) put(out, VARY ? jp_pos(jp[it]) : tid + it * WG, jvals[it]);
         // entries in the horizon-global columns (constants) sit right behind the last knot's block: the last knot writes them
         if constexpr (!VARY) { if (last && tid < n_glob && (!SPLIT || jpg >= 0)) a.jac[int64_t(b) * a.jac_stride + (int64_t(jac_glob_base) - a.jac_off) + tid] = s.jac[SPLIT ? max(jpg, 0) : jpg]; }
     }
     if (a.g) {
         double* out = a.g + size_t(b) * a.m;
 #pragma unroll
-        for (int it = 0; it < G_ITERS; ++it) if (ga[it] != G_NONE && !(early_on && (gb[it] & COPY_EARLY))) out[ga[it] + gb_stride(gb[it]) * k] = gvals[it];
+        for (int it = 0; it < G_ITERS; ++it) if (ga[it] != G_NONE && !(early_on && (gb[it] & COPY_EARLY))) put(out, ga[it] + gb_stride(gb[it]) * k, gvals[it]);
     }
     if (a.g_stage) {
         bool dense = false;
@@ -684,7 +693,7 @@ void hipnlp_knot_kernel(const DeviceTables* tb_p, const double* x_p, const doubl
     if (a.grad) {
         double* out = a.grad + int64_t(b) * a.grad_stride + (int64_t(NXK) * k - a.grad_off);
 #pragma unroll
-        for (int it = 0; it < GR_ITERS; ++it) { const int i = tid + it * WG; if (i < NXK && (!SPLIT || split_grad_is_model_free(i) == wg_m)) out[i] = grvals[it]; }
+        for (int it = 0; it < GR_ITERS; ++it) { const int i = tid + it * WG; if (i < NXK && (!SPLIT || split_grad_is_model_free(i) == wg_m)) put(out, i, grvals[it]); }
         if (last && tid < NXG && !wg_m) a.grad[int64_t(b) * a.grad_stride + (int64_t(NXK) * N - a.grad_off) + tid] = 0.0;  // the global variables carry no cost
     }
     if (anybad && lane == 0) {   // generation flag: nothing to reset between launches
@@ -1565,6 +1574,7 @@ struct hipnlp_handle {
     // two workgroups per knot (SPLIT instantiations): device-resident launches of the eight-wave kernels that leave at least half of the
     // CUs idle — (2 knots + 1) x batch workgroups on 256 CUs, one each — and whose horizon ends are not costs (knot_body.h)
     bool split = false;
+    bool last_split = false;   // the last knot launch ran two workgroups per knot (read by the diagnostic build's hipnlp_debug_last_launch)
     bool fused = false;  // the total cost is summed inside the knot launch by one reducer workgroup per trajectory (knots <= 256)
     hipnlp_dims dims{};         // hipnlp_get_dims, filled by hipnlp_create
     bool early_store_always = false;   // diagnostic (HIPNLP_EARLY_STORE=2): also for hipnlp_eval_device launches
@@ -2384,6 +2394,7 @@ static int launch(hipnlp_handle* h, const double* x_dev, double* f_dev, double* 
     const bool split = h->split && fused && !peer_out && !g_stage && !host_block && !a.early && !compact;
     const dim3 grid((split ? 2u : 1u) * unsigned(h->nk) + (fused ? 1u : 0u), unsigned(h->batch));   // (+ the row's cost reducer)
     const bool planar = h->d.settings.terrain == HIPNLP_TERRAIN_PLANAR;
+    h->last_split = split;
     if (split) {
         if (vary_only) {
             if (planar) hipLaunchKernelGGL((hipnlp_knot_kernel<HIPNLP_TERRAIN_PLANAR, 8, false, true, false, true>), grid, dim3(512), 0, s, a.tb, a.x, a.pk, a.gp, a.N, a.n, a.knot_begin, a.nk, a);
@@ -4178,6 +4189,21 @@ int hipnlp_profile_end(hipnlp_handle* h, double* mean_knot_kernel_ms, double* me
     h->timing_valid = false;
     return HIPNLP_OK;
 }
+
+#ifdef HIPNLP_DIAG
+// diagnostic build only (tests): workgroups per knot of the handle's last knot launch, and its non-finite flag per trajectory
+// (raised[b] = 1: the launch produced a NaN / Inf in trajectory b) — what a host-path call reports as HIPNLP_E_NUMERIC.  Synchronises.
+int hipnlp_debug_last_launch(hipnlp_handle* h, int* workgroups_per_knot, int32_t* raised /*[batch]*/) {
+    if (!h || !workgroups_per_knot || !raised) return HIPNLP_E_INVALID;
+    NOT_FRONT(h, "hipnlp_debug_last_launch");
+    HIP_TRY(h, hipSetDevice(h->dev));
+    HIP_TRY(h, hipDeviceSynchronize());   // (the launch may sit on a stream of the caller's)
+    HIP_TRY(h, hipnlp_internal_memcpy(raised, h->d_flag, size_t(h->batch) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int b = 0; b < h->batch; ++b) raised[b] = raised[b] == int32_t(h->seq) ? 1 : 0;   // (a generation flag: the number of the launch that raised it)
+    *workgroups_per_knot = h->last_split ? 2 : 1;
+    return HIPNLP_OK;
+}
+#endif
 
 #ifdef HIPNLP_STAMPS
 int hipnlp_debug_stamps(hipnlp_handle* h, unsigned long long* out /*[nk*batch][4][16]*/) {
