@@ -16,6 +16,10 @@
     gx = J.rmatvec(sigma, lam)                             # sigma grad f + J^T lam     (hipnlp_jac_transpose_times_device)
     dot, jv = nlp.jacobian_vector_product(x, v)            # the two launches above (evaluate, multiply) in one call
 
+    K = nlp.kkt(x, sigma, lam, dx, dc)                     # the KKT operator [[H + diag dx, J^T], [J, -diag dc]] at one x: the two value runs
+    top, bottom = K.matvec(v, w)                           # (H + diag dx) v + J^T w [B, n] and J v - dc w [B, m], ONE launch (hipnlp_kkt_times_device)
+    K2 = K.with_diagonals(dx2, dc2)                        # other diagonals on the same value runs: no launch
+
 The forward pass is hipnlp_eval_device with grad f and jac g left out; the backward pass is the Lagrangian gradient
 sigma grad f + J^T lambda with sigma = df, lambda = dg (zeros for an output whose gradient is None): the Jacobian never reaches memory.
 All launches run on torch.cuda.current_stream().
@@ -216,6 +220,47 @@ class JacobianValues:
         return dot, jv
 
 
+class KKTValues:
+    """The KKT operator of an interior-point step at one (x, sigma, lam),
+
+        K = [ H + diag dx    J^T      ]
+            [ J             -diag dc  ]
+
+    on the value runs of `hessian_values` (HessianValues or a [batch, nnz_h] tensor of hipnlp_eval_hess_device) and `jacobian_values`
+    (JacobianValues or a [batch, nnz] tensor of hipnlp_eval_device), both of nlp's own handle.  dx [batch, n] and dc [batch, m] are the
+    primal-dual diagonals (None: left out).  matvec(v, w) is ONE launch (hipnlp_kkt_times_device) — what the inner iterations of a Krylov
+    solve on the KKT system call; with_diagonals(dx, dc) is the same operator with other diagonals, without a launch.  Not recorded by
+    autograd."""
+
+    def __init__(self, nlp, hessian_values, jacobian_values, dx=None, dc=None):
+        self.nlp = nlp
+        self.hess = hessian_values.values if isinstance(hessian_values, HessianValues) else hessian_values
+        self.jac = jacobian_values.values if isinstance(jacobian_values, JacobianValues) else jacobian_values
+        nlp._check("hessian values", self.hess, (nlp.batch, nlp.engine.hess_nnz()))
+        nlp._check("jacobian values", self.jac, (nlp.batch, nlp.engine.nnz))
+        if dx is not None:
+            nlp._check("dx", dx, (nlp.batch, nlp.n))
+        if dc is not None:
+            nlp._check("dc", dc, (nlp.batch, nlp.m))
+        self.dx, self.dc = dx, dc
+
+    def with_diagonals(self, dx=None, dc=None):
+        """the operator on the same value runs with the diagonals dx [batch, n] and dc [batch, m] (None: left out); no launch"""
+        return KKTValues(self.nlp, self.hess, self.jac, dx, dc)
+
+    def matvec(self, v, w):
+        """(top [batch, n], bottom [batch, m]) = K [v; w], v [batch, n], w [batch, m]; one launch"""
+        torch, nlp = _torch(), self.nlp
+        nlp._check("v", v, (nlp.batch, nlp.n))
+        nlp._check("w", w, (nlp.batch, nlp.m))
+        top = torch.empty_like(v, memory_format=torch.contiguous_format)
+        bottom = torch.empty_like(w, memory_format=torch.contiguous_format)
+        nlp._on_current_stream(lambda s: nlp.engine.kkt_times_device(self.hess.data_ptr(), self.jac.data_ptr(), v.data_ptr(), w.data_ptr(), top.data_ptr(), bottom.data_ptr(),
+                                                                     dx_ptr=self.dx.data_ptr() if self.dx is not None else 0,
+                                                                     dc_ptr=self.dc.data_ptr() if self.dc is not None else 0, stream=s))
+        return top, bottom
+
+
 class _DeviceNLP:
     """what the two NLPs share: an engine handle on cuda:`device_index` with batch, n, m, np; tensors checked to be float64, contiguous and
     on that device; launches ordered on torch.cuda.current_stream()"""
@@ -333,6 +378,12 @@ class KinodynamicNLP(_DeviceNLP):
         values = torch.empty(self.batch, self.engine.hess_nnz(), dtype=torch.float64, device=self.device)
         self._on_current_stream(lambda s: self.engine.eval_hess_device(x.data_ptr(), sigma.data_ptr(), lam.data_ptr(), values.data_ptr(), stream=s))
         return HessianValues(self, values)
+
+    def kkt(self, x, sigma, lam, dx=None, dc=None):
+        """KKTValues at (x, sigma, lam) with the diagonals dx [batch, n] and dc [batch, m] (None: left out): the two evaluation launches
+        of jacobian(x) and hessian(x, sigma, lam); .matvec(v, w) applies [[H + diag dx, J^T], [J, -diag dc]] in one launch.  Not recorded
+        by autograd."""
+        return KKTValues(self, self.hessian(x, sigma, lam), self.jacobian(x), dx, dc)
 
     # ---- internals ------------------------------------------------------------------------------------------------------------------
     def _forward(self, x, f, g):

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "knot_hess_layout.h"
+#include "knot_kkt.h"
 #include "knot_stage.h"
 #include "layout.h"
 
@@ -1423,6 +1424,192 @@ void hipnlp_jac_transpose_times_kernel(JTArgs a) {
         a.out[int64_t(b) * a.n + int64_t(NXK) * k + tid] = jprod_column_staged(with_grad, sig, gc, e0, e1, lw, ls, js);
     } else if (last && tid >= LG_SPAN_GLOB && tid < LG_SPAN_GLOB + NXG) {   // the global variables carry no cost
         a.out[int64_t(b) * a.n + int64_t(NXK) * N + (tid - LG_SPAN_GLOB)] = jprod_column_staged(with_grad, sig, 0.0, e0, e1, lw, ls, js);
+    }
+}
+
+
+// =====================================================================================================================
+// The KKT operator of an interior-point step from stored value runs (hipnlp_kkt_times_device; knot_kkt.h):
+//     top [n] = (H + diag d_x) v + J^T w,     bottom [m] = J v - diag(d_c) w
+// in ONE launch — what a Krylov solve on the KKT system at a fixed x multiplies by, with diagonals that change between solves.  One
+// workgroup per (trajectory, knot), as the three stored-values kernels above, and nothing but their sums: H is block diagonal by knot,
+// the columns of jac g are knot-local, every row of g has one owner knot.  No knot program, no x, no parameters, no non-finite flag, no
+// atomics, no exchange between workgroups.
+//   loads: everything is requested before the first LDS write (one memory round trip; only the multipliers of the owned rows and of the
+//   column sums wait for their table words first): the own and the predecessor's block of the jac run, the extras (the last knot's
+//   entries of knot 0's block, the horizon-global run at knot 0 — and at the last knot, for its six global columns), the records of v,
+//   the multipliers w of LgradTables::row_a / row_b, the knot's block of the Hessian run with the coupling value, the three word tables.
+//   phase 1: the jac values, both entry-word tables, v and w go into LDS; after the barrier every thread finishes its column of J^T w
+//   (jprod_column_staged, as hipnlp_jac_transpose_times_kernel without a gradient) and its one or two owned rows of J v
+//   (jprod_row_staged, as hipnlp_jac_times_kernel) INTO REGISTERS, and stores its rows of bottom.
+//   phase 2: behind a second barrier the Hessian block and its touch words, held in registers until then, are written over the dead jac
+//   values and entry words (the records of v stay); behind a third barrier hvp_thread_row, as hipnlp_hess_times_kernel calls it, and
+//   kkt_top: (H v)_c + (J^T w)_c, then one fused multiply-add with d_x.  The last knot's threads LG_SPAN_GLOB .. write the six
+//   horizon-global elements with +0.0 for the Hessian part.
+// Side by side the three kernels' arrays come to 84 736 B — one workgroup per CU; overlaid, 54 144 B: two (43 granules of 1 280 B each).
+// Every element of top and bottom is written exactly once per trajectory; nothing else is written.
+// =====================================================================================================================
+struct KktArgs {
+    const JprodTables* jt;
+    const LgradTables* tt;   // (block positions: the tables of hipnlp_jac_transpose_times_kernel)
+    const HvpTables* vt;
+    const double* hvals;    // [batch][nnz_h]
+    const double* jvals;    // [batch][nnz]
+    const double* dx;       // [batch][n] or null
+    const double* dc;       // [batch][m] or null
+    const double* v;        // [batch][n]
+    const double* w;        // [batch][m]
+    double* top;            // [batch][n]
+    double* bottom;         // [batch][m]
+    int32_t N, n, m, nnz_first, nnz_interior, nnz_last, nnz_glob, nnz_knot, n_couple;
+    int64_t nnz, glob_base, nnz_h;
+};
+// the LDS of a workgroup, in doubles: the records of v live through both phases; the Hessian block and its touch words lie over the jac
+// values and the row entry words
+constexpr int KK_HB = (hk::COUNT + JP_WG - 1) / JP_WG;
+constexpr int KK_VS = 0, KK_JS = KK_VS + JP_V_WORDS, KK_TW = KK_JS + JP_VALUES, KK_LW = KK_TW + JP_ENT_CAP / 2, KK_LS = KK_LW + (LG_ENT_CAP + 16) / 2;
+constexpr int KK_JG = KK_LS + LG_LAM_CAP, KK_WORDS = KK_JG + 16;
+constexpr int KK_HV = KK_JS, KK_HW = KK_HV + KK_HB * JP_WG;
+static_assert(JP_V_WORDS % 2 == 0 && JP_VALUES % 2 == 0 && JP_ENT_CAP % 4 == 0 && (LG_ENT_CAP + 16) % 4 == 0 && LG_LAM_CAP % 2 == 0, "16-byte aligned LDS arrays");
+static_assert(KK_HW + HVP_WORD_CAP / 2 <= KK_WORDS && HVP_WORD_CAP % 2 == 0, "the Hessian block and its touch words fit over the dead arrays");
+static_assert(KK_JG >= LG_ENT_CAP && JP_GLOB_CAP <= 16, "the horizon-global run of the last knot is addressed from LG_ENT_CAP on");
+static_assert(2 * ((KK_WORDS * int(sizeof(double)) + 1279) / 1280) * 1280 <= 160 * 1024, "two workgroups per CU");
+static_assert(LG_SPAN_GLOB == JP_V_STRIDE && LG_SPAN_GLOB == HVP_SPAN_GLOB, "the threads of the global columns stage the global elements of v");
+__global__ __launch_bounds__(JP_WG)
+void hipnlp_kkt_times_kernel(KktArgs a) {
+    constexpr int WG = JP_WG, JB = JP_BLOCK_CAP / WG, LQ = LG_LAM_CAP / WG, RQ = JP_ROW_CAP / WG, HB = KK_HB;
+    static_assert(JP_BLOCK_CAP % WG == 0 && JP_OTHER_CAP <= WG && JP_GLOB_CAP <= WG && JP_V_STRIDE <= WG && LG_ENT_CAP == JP_BLOCK_CAP && WG == 256, "kkt staging by 256 threads");
+    __shared__ alignas(16) double lds[KK_WORDS];
+    double* vs = lds + KK_VS;
+    double* js = lds + KK_JS;
+    int32_t* tw = reinterpret_cast<int32_t*>(lds + KK_TW);
+    int32_t* lw = reinterpret_cast<int32_t*>(lds + KK_LW);
+    double* ls = lds + KK_LS;
+    double* jg = lds + KK_JG;
+    double* hv = lds + KK_HV;
+    int32_t* hw = reinterpret_cast<int32_t*>(lds + KK_HW);
+    const int tid = threadIdx.x;
+    const int b = blockIdx.y, k = blockIdx.x, N = a.N;
+    const int first = k == 0, last = k == N - 1;
+    const int pv = first ? PV_FIRST : (last ? PV_LAST : (k == 1 ? PV_SECOND : PV_INTERIOR));
+    const int bv = first ? VAR_FIRST : (last ? VAR_LAST : VAR_INTERIOR);
+    const JprodTables& jt = *a.jt;
+    const LgradTables& lt = *a.tt;
+    const HvpTables& vt = *a.vt;
+    const double* jvals = a.jvals + int64_t(b) * a.nnz;
+    const double* hvals = a.hvals + int64_t(b) * a.nnz_h;
+    const double* vb = a.v + int64_t(b) * a.n;
+    const double* wb = a.w + int64_t(b) * a.m;
+    const bool with_dx = a.dx != nullptr, with_dc = a.dc != nullptr;
+    auto block_len = [&](int kk) __attribute__((always_inline)) { return kk == 0 ? a.nnz_first : (kk == N - 1 ? a.nnz_last : a.nnz_interior); };
+    auto block_base = [&](int kk) __attribute__((always_inline)) { return kk == 0 ? int64_t(0) : int64_t(a.nnz_first) + int64_t(kk - 1) * a.nnz_interior; };
+    const bool col_thread = tid < NXK, glob_thread = last && tid >= LG_SPAN_GLOB && tid < LG_SPAN_GLOB + NXG;
+    // ---- the table words first: the multipliers are addressed by them
+    int32_t ra[RQ], rb[RQ], dir[RQ], la[LQ], lb[LQ];
+#pragma unroll
+    for (int it = 0; it < RQ; ++it) { const int q = tid + it * WG; ra[it] = jt.row_a[pv][q]; rb[it] = jt.row_b[pv][q]; dir[it] = jt.rdir[pv][q]; }
+#pragma unroll
+    for (int it = 0; it < LQ; ++it) { la[it] = lt.row_a[bv][tid + it * WG]; lb[it] = lt.row_b[bv][tid + it * WG]; }
+    // ---- the jac run: own block, predecessor's block, the extras
+    const int n_own = block_len(k), n_pred = first ? 0 : block_len(k - 1);
+    const double* own = jvals + block_base(k);
+    const double* pred = jvals + block_base(first ? 0 : k - 1);
+    double o[JB], p[JB];
+#pragma unroll
+    for (int it = 0; it < JB; ++it) { const int i = tid + it * WG; o[it] = i < n_own ? own[i] : 0.0; }
+#pragma unroll
+    for (int it = 0; it < JB; ++it) { const int i = tid + it * WG; p[it] = i < n_pred ? pred[i] : 0.0; }
+    double ex = 0.0;   // the entries of knot 0's block a last knot needs (threads 0 ..), the horizon-global run at knot 0 (threads 128 ..)
+    if (tid < JP_OTHER_CAP) {
+        const int32_t q = jt.other[tid];
+        if (last && q >= 0 && q < a.nnz_first) ex = jvals[q];
+    } else if (tid - JP_OTHER_CAP < JP_GLOB_CAP) {
+        const int i = tid - JP_OTHER_CAP;
+        if (first && i < a.nnz_glob) ex = jvals[a.glob_base + i];
+    }
+    const double og = (last && tid < 16 && tid < a.nnz_glob) ? jvals[a.glob_base + tid] : 0.0;   // the same run for the last knot's global columns
+    // ---- the records of v (own knot, predecessor, other horizon end, globals) and this thread's element of d_x
+    double v0 = 0.0, v1 = 0.0, v2 = 0.0, dxc = 0.0;
+    if (tid < JP_V_STRIDE) {
+        if (col_thread) {
+            v0 = vb[int64_t(NXK) * k + tid];
+            if (!first) v1 = vb[int64_t(NXK) * (k - 1) + tid];
+            if (last) v2 = vb[tid];
+            if (with_dx) dxc = a.dx[int64_t(b) * a.n + int64_t(NXK) * k + tid];
+        }
+    } else if (tid - JP_V_STRIDE < JP_V_WORDS - JP_V_GLOB) {
+        const int i = tid - JP_V_STRIDE;
+        if (i < NXG) v0 = vb[int64_t(NXK) * N + i];
+        if (glob_thread && with_dx) dxc = a.dx[int64_t(b) * a.n + int64_t(NXK) * N + i];
+    }
+    // ---- the entry words of rows and columns
+    int32_t wr[JP_WORDS_PER_THREAD], cw[JB];
+#pragma unroll
+    for (int it = 0; it < JP_WORDS_PER_THREAD; ++it) wr[it] = jt.word[pv][tid + it * WG];
+#pragma unroll
+    for (int it = 0; it < JB; ++it) cw[it] = lt.word[bv][tid + it * WG];
+    const int32_t cwg = lt.word[bv][LG_ENT_CAP + (tid & 15)];
+    const int32_t e0 = lt.beg[bv][tid], e1 = lt.end[bv][tid];
+    // ---- the multipliers: those of the column sums, and w_i / d_c,i of the owned rows
+    double lv[LQ], wq[RQ], dcq[RQ];
+#pragma unroll
+    for (int it = 0; it < LQ; ++it) lv[it] = la[it] != G_NONE ? wb[la[it] + lb[it] * k] : 0.0;
+#pragma unroll
+    for (int it = 0; it < RQ; ++it) {
+        const bool on = ra[it] != G_NONE && with_dc;
+        wq[it] = on ? wb[ra[it] + rb[it] * k] : 0.0;
+        dcq[it] = on ? a.dc[int64_t(b) * a.m + ra[it] + rb[it] * k] : 0.0;
+    }
+    // ---- the Hessian run: the knot's block, its touch words, the coupling term of both horizon ends (held in registers across phase 1)
+    const double* blk = hvals + int64_t(a.nnz_knot) * k;
+    double h[HB];
+    int32_t hwr[HVP_WORDS_PER_THREAD];
+#pragma unroll
+    for (int it = 0; it < HB; ++it) { const int i = tid + it * WG; h[it] = i < a.nnz_knot ? blk[i] : 0.0; }
+#pragma unroll
+    for (int it = 0; it < HVP_WORDS_PER_THREAD; ++it) hwr[it] = vt.word_pos[tid + it * WG];
+    const int32_t row = vt.row[tid];
+    const bool ends_coupled = a.n_couple > 0 && (first || last);
+    double vo = 0.0, cpl = 0.0;
+    if (col_thread && ends_coupled && ((row >> HVP_COUPLED_BIT) & 1)) {
+        vo = vb[int64_t(NXK) * (first ? N - 1 : 0) + tid];
+        cpl = hvals[int64_t(a.nnz_knot) * N + vt.couple[tid]];
+    }
+    // ---- phase 1: jac values, entry words, v and w -> LDS
+    if (tid < JP_V_STRIDE) { vs[tid] = v0; vs[JP_V_PRED + tid] = v1; vs[JP_V_OTHER + tid] = v2; }
+    else if (tid - JP_V_STRIDE < JP_V_WORDS - JP_V_GLOB) vs[JP_V_GLOB + (tid - JP_V_STRIDE)] = v0;
+#pragma unroll
+    for (int it = 0; it < JB; ++it) { js[tid + it * WG] = o[it]; js[JP_POS_PRED + tid + it * WG] = p[it]; lw[tid + it * WG] = cw[it]; }
+#pragma unroll
+    for (int it = 0; it < JP_WORDS_PER_THREAD; ++it) tw[tid + it * WG] = wr[it];
+#pragma unroll
+    for (int it = 0; it < LQ; ++it) ls[tid + it * WG] = lv[it];
+    if (tid < JP_OTHER_CAP + JP_GLOB_CAP) js[JP_POS_OTHER + tid] = ex;   // (JP_POS_GLOB == JP_POS_OTHER + JP_OTHER_CAP)
+    if (tid < 16) { jg[tid] = og; lw[LG_ENT_CAP + tid] = cwg; }
+    __syncthreads();
+    // the column of J^T w (the horizon-global columns read their run from jg: the words address it from LG_ENT_CAP on)
+    double jtc = 0.0;
+    if (col_thread) jtc = jprod_column_staged(false, 0.0, 0.0, e0, e1, lw, ls, js);
+    else if (glob_thread) jtc = jprod_column_staged(false, 0.0, 0.0, e0, e1, lw, ls, jg - LG_ENT_CAP);
+    // the owned rows of J v, and bottom
+    {
+        double* out = a.bottom + int64_t(b) * a.m;
+#pragma unroll
+        for (int it = 0; it < RQ; ++it)
+            if (ra[it] != G_NONE) out[ra[it] + rb[it] * k] = kkt_bottom(with_dc, dcq[it], wq[it], jprod_row_staged(dir[it], tw, js, vs));
+    }
+    __syncthreads();   // every sum over the jac values is in registers: their LDS is dead
+    // ---- phase 2: the Hessian block and its touch words over it
+#pragma unroll
+    for (int it = 0; it < HB; ++it) hv[tid + it * WG] = h[it];
+#pragma unroll
+    for (int it = 0; it < HVP_WORDS_PER_THREAD; ++it) hw[tid + it * WG] = hwr[it];
+    __syncthreads();
+    if (col_thread) {
+        const double y = hvp_thread_row(ends_coupled ? row : row & ~(1 << HVP_COUPLED_BIT), hw, vs, [&](int pos) __attribute__((always_inline)) { return hv[pos]; }, cpl, vo);
+        a.top[int64_t(b) * a.n + int64_t(NXK) * k + tid] = kkt_top(with_dx, dxc, v0, y, jtc);
+    } else if (glob_thread) {   // no entry of the Hessian touches the horizon-global variables
+        a.top[int64_t(b) * a.n + int64_t(NXK) * N + (tid - LG_SPAN_GLOB)] = kkt_top(with_dx, dxc, v0, 0.0, jtc);
     }
 }
 
@@ -3107,6 +3294,28 @@ int hipnlp_jac_transpose_times_device(hipnlp_handle* h, const double* jac_values
     a.nnz_first = L.nnz_v[VAR_FIRST]; a.nnz_interior = L.nnz_v[VAR_INTERIOR]; a.nnz_last = L.nnz_v[VAR_LAST]; a.nnz_glob = int32_t(L.jperm_glob.size());
     a.nnz = L.nnz; a.glob_base = L.jac_glob_base;
     hipLaunchKernelGGL(hipnlp_jac_transpose_times_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(256), 0, stream ? hipStream_t(stream) : h->stream, a);
+    HIP_TRY(h, hipGetLastError());
+    return HIPNLP_OK;
+}
+// ---- the KKT operator from stored value runs (include/hipnlp.h) ---------------------------------------------------------------------------
+int hipnlp_kkt_times_device(hipnlp_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev, const double* dc_dev, const double* v_dev,
+                            const double* w_dev, double* top_dev, double* bottom_dev, void* stream) {
+    if (!h || !hess_values_dev || !jac_values_dev || !v_dev || !w_dev || !top_dev || !bottom_dev) return HIPNLP_E_INVALID;
+    NOT_FRONT(h, "hipnlp_kkt_times_device");
+    if (const int rc = whole_horizon_only(h, "hipnlp_kkt_times_device", "a row of g has entries in the blocks of two knots, the periodicity coupling needs both horizon ends")) return rc;
+    const Layout& L = h->L;
+    if (!L.lgrad_ok) { h->err = "hipnlp_kkt_times_device: " + L.lgrad_error; return HIPNLP_E_UNSUPPORTED; }
+    if (const int rc = jprod_prepare(h, "hipnlp_kkt_times_device")) return rc;
+    if (const int rc = hvp_prepare(h, "hipnlp_kkt_times_device")) return rc;
+    HIP_TRY(h, hipSetDevice(h->dev));
+    KktArgs a;
+    a.jt = h->d_jt; a.tt = h->d_jtt; a.vt = h->d_vt; a.hvals = hess_values_dev; a.jvals = jac_values_dev; a.dx = dx_dev; a.dc = dc_dev;
+    a.v = v_dev; a.w = w_dev; a.top = top_dev; a.bottom = bottom_dev;
+    a.N = L.N; a.n = L.n; a.m = L.m;
+    a.nnz_first = L.nnz_v[VAR_FIRST]; a.nnz_interior = L.nnz_v[VAR_INTERIOR]; a.nnz_last = L.nnz_v[VAR_LAST]; a.nnz_glob = int32_t(L.jperm_glob.size());
+    a.nnz_knot = h->HL.nnz_knot; a.n_couple = h->HL.n_couple;
+    a.nnz = L.nnz; a.glob_base = L.jac_glob_base; a.nnz_h = hess_count(h);
+    hipLaunchKernelGGL(hipnlp_kkt_times_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(JP_WG), 0, stream ? hipStream_t(stream) : h->stream, a);
     HIP_TRY(h, hipGetLastError());
     return HIPNLP_OK;
 }

@@ -28,7 +28,7 @@ EXPORTS = [
     "hipnlp_device_numa_node", "hipnlp_pin_thread_to_device_numa_node",
     "hipnlp_hess_nnz", "hipnlp_hess_sparsity", "hipnlp_eval_hess", "hipnlp_eval_hess_at", "hipnlp_set_hessian_early_run", "hipnlp_get_hessian_early_run", "hipnlp_hessian_early_run_reason", "hipnlp_eval_hess_device",
     "hipnlp_eval_lagrangian_grad_device", "hipnlp_eval_hess_vec_device", "hipnlp_hess_times_device",
-    "hipnlp_jac_times_device", "hipnlp_jac_transpose_times_device",
+    "hipnlp_jac_times_device", "hipnlp_jac_transpose_times_device", "hipnlp_kkt_times_device",
     "hipnlp_eval_pinned", "hipnlp_set_prefetch", "hipnlp_set_early_outputs", "hipnlp_set_host_timing", "hipnlp_host_register", "hipnlp_host_unregister",
     "hipnlp_multi_create", "hipnlp_multi_plan", "hipnlp_multi_info", "hipnlp_multi_breakdown", "hipnlp_multi_set_threads",
     "hipnlp_host_breakdown", "hipnlp_set_auto_register", "hipnlp_host_stats", "hipnlp_set_constant_jacobian", "hipnlp_forget_jac_destination", "hipnlp_jac_constant_mask", "hipnlp_host_release_auto_ranges",
@@ -220,6 +220,8 @@ def load_library(path=None):
     if hasattr(lib, "hipnlp_jac_times_device"):
         lib.hipnlp_jac_times_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
         lib.hipnlp_jac_transpose_times_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "hipnlp_kkt_times_device"):
+        lib.hipnlp_kkt_times_device.argtypes = [vp] * 10
     _libs[path] = lib
     return lib
 
@@ -614,6 +616,14 @@ class HipNlp:
         vp = C.c_void_p
         self._check(self.lib.hipnlp_jac_transpose_times_device(self.h, vp(jac_values_ptr or None), vp(grad_values_ptr or None), vp(obj_factor_ptr or None),
                                                                vp(lam_ptr or None), vp(out_ptr or None), vp(stream or None)))
+
+    def kkt_times_device(self, hess_values_ptr, jac_values_ptr, v_ptr, w_ptr, top_ptr, bottom_ptr, dx_ptr=0, dc_ptr=0, stream=0):
+        """top [batch][n] = (H + diag dx) v + J^T w and bottom [batch][m] = J v - diag(dc) w in ONE launch (hipnlp_kkt_times_device), from
+        the Hessian run [batch][nnz_h] eval_hess_device and the jac run [batch][nnz] eval_device of this handle wrote; dx [batch][n] and
+        dc [batch][m] are optional (0: that term is left out); asynchronous on `stream`; the outputs may not alias the inputs"""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_kkt_times_device(self.h, vp(hess_values_ptr or None), vp(jac_values_ptr or None), vp(dx_ptr or None), vp(dc_ptr or None),
+                                                     vp(v_ptr or None), vp(w_ptr or None), vp(top_ptr or None), vp(bottom_ptr or None), vp(stream or None)))
 
     def cost_terms(self):
         out = np.empty((self.batch, _abi.NCOST_TERMS))

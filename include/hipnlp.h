@@ -477,6 +477,35 @@ int hipnlp_jac_times_device(hipnlp_handle* h, const double* jac_values_dev, cons
 int hipnlp_jac_transpose_times_device(hipnlp_handle* h, const double* jac_values_dev, const double* grad_values_dev,
                                       const double* obj_factor_dev, const double* lambda_dev, double* out_dev, void* stream);
 
+/* The KKT operator of an interior-point step, applied to a vector, from STORED value runs — the object a Krylov solve on the KKT system at
+ * a fixed x multiplies by, in ONE launch instead of hipnlp_hess_times_device + hipnlp_jac_times_device +
+ * hipnlp_jac_transpose_times_device and the element-wise kernels between them:
+ *
+ *     top_dev    [batch][n] = (H + diag d_x) v + J^T w
+ *     bottom_dev [batch][m] =  J v - diag(d_c) w
+ *
+ * hess_values_dev [batch][nnz_h] is a run as hipnlp_eval_hess_device of the SAME handle wrote it (H = H(x, obj_factor, lambda) of that
+ * call), jac_values_dev [batch][nnz] a jac run as hipnlp_eval_device of the same handle wrote it (its order, CCS or
+ * HIPNLP_FLAG_JAC_VARYING_FIRST, the constant entries included).  v_dev, dx_dev, top_dev [batch][n]; w_dev, dc_dev, bottom_dev [batch][m]
+ * (m of THIS handle: the reduced rows of a HIPNLP_FLAG_DETECT_SIMPLE_BOUNDS handle).  dx_dev and dc_dev are the primal-dual diagonals
+ * (Sigma + delta_x and delta_c): they change between solves at one x and are arguments of every call; either may be NULL (that term is
+ * left out, nothing is read).  No knot program runs: no x, no parameters, no non-finite flag.  Device pointers, enqueued on `stream`
+ * (NULL = the handle's own), not synchronised; stream rules of hipnlp_hess_times_device.  The outputs may not alias the inputs.
+ *
+ * Order of every sum (knot_kkt.h): one workgroup per knot;  hv_c = (H v)_c exactly as hipnlp_hess_times_device sums it (+0.0 for the six
+ * horizon-global variables),  jt_c = (J^T w)_c exactly as hipnlp_jac_transpose_times_device sums it without a gradient,
+ * top_c = hv_c + jt_c,  with dx_dev: top_c = fma(d_x,c, v_c, hv_c + jt_c);  jv_i = (J v)_i exactly as hipnlp_jac_times_device sums it by
+ * the row's owner knot,  bottom_i = jv_i,  with dc_dev: bottom_i = fma(-d_c,i, w_i, jv_i).  Without diagonals the result is bit for bit the
+ * composition of the three launches and one addition; the same bits at every position of a batch and for both jac orders.  Every element
+ * of top_dev and bottom_dev is written exactly once; nothing else is written.
+ *
+ * Returns HIPNLP_E_INVALID for a missing handle or required pointer (all but dx_dev and dc_dev), HIPNLP_E_UNSUPPORTED on a multi-device
+ * handle, on a shard handle (knot_begin / knot_end not the whole horizon) and for a layout whose tables exceed what the kernel stages
+ * (hipnlp_last_error says which).  No HIPNLP_E_PARAMS. */
+int hipnlp_kkt_times_device(hipnlp_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev,
+                            const double* dc_dev, const double* v_dev, const double* w_dev, double* top_dev, double* bottom_dev,
+                            void* stream);
+
 /* Sharded variant (multi-GPU): the handle owns knots [knot_begin, knot_end).  Outputs are
  * shard-local and contiguous so that one RCCL all-gather reassembles them:
  *   grad_shard [batch][shard_grad]  = grad f entries of the shard's knots (+ the 6 global entries on the last shard)
