@@ -19,6 +19,7 @@
     K = nlp.kkt(x, sigma, lam, dx, dc)                     # the KKT operator [[H + diag dx, J^T], [J, -diag dc]] at one x: the two value runs
     top, bottom = K.matvec(v, w)                           # (H + diag dx) v + J^T w [B, n] and J v - dc w [B, m], ONE launch (hipnlp_kkt_times_device)
     K2 = K.with_diagonals(dx2, dc2)                        # other diagonals on the same value runs: no launch
+    z = K.solve(b_top, b_bottom, rtol=1e-8, maxiter=200)   # K [z.top; z.bottom] = b by MINRES on the device (hipnlp_kkt_minres_device); z.status
 
 The forward pass is hipnlp_eval_device with grad f and jac g left out; the backward pass is the Lagrangian gradient
 sigma grad f + J^T lambda with sigma = df, lambda = dg (zeros for an output whose gradient is None): the Jacobian never reaches memory.
@@ -47,6 +48,7 @@ A pose is one workgroup, which holds all of jac g and of the Hessian in LDS: the
 sigma and lam, grad f . w and J w, are one launch too, so a double backward through any loss in f and g — (f ** 2).sum() + (g ** 2).sum()
 — runs: H w from one launch when x needs it, grad f . w and J w from one launch when sigma or lam needs it.  Nothing raises.
 torch is imported when first needed."""
+import collections
 import numbers
 
 import numpy as np
@@ -259,6 +261,46 @@ class KKTValues:
                                                                      dx_ptr=self.dx.data_ptr() if self.dx is not None else 0,
                                                                      dc_ptr=self.dc.data_ptr() if self.dc is not None else 0, stream=s))
         return top, bottom
+
+    def solve(self, rhs_top, rhs_bottom, rtol=1e-8, maxiter=200, minv=None, check_every=16):
+        """KKTSolution(top [batch, n], bottom [batch, m], iterations [batch] int32, residual [batch], status [batch] int32) of
+        K [top; bottom] = [rhs_top; rhs_bottom] by preconditioned MINRES from a zero start, resident on the device
+        (hipnlp_kkt_minres_device: three launches per iteration, the scalars never visit the host).  minv: a pair (top [batch, n], bottom
+        [batch, m]) of positive diagonals, the preconditioner M^-1 (None: the identity).  status 0: residual <= rtol, the relative
+        residual in the M^-1 norm; 1: maxiter reached; 2: breakdown (minv not positive, or data that is not finite).  check_every = k > 0
+        waits for the stream after every k iterations and stops once every trajectory has a status; 0 enqueues maxiter iterations
+        without ever waiting — the same bits.  The solves of one nlp share a workspace: keep them on one stream.  Not recorded by
+        autograd: a right-hand side that requires grad gets a solution without a graph.  No convergence is promised on the KKT systems of
+        real iterates (indefinite, badly scaled; no preconditioner is built here)."""
+        torch, nlp = _torch(), self.nlp
+        nlp._check("rhs_top", rhs_top, (nlp.batch, nlp.n))
+        nlp._check("rhs_bottom", rhs_bottom, (nlp.batch, nlp.m))
+        if not (isinstance(rtol, numbers.Real) and rtol >= 0.0):
+            raise ValueError("rtol: a real number >= 0, not %r" % (rtol,))
+        for name, k in (("maxiter", maxiter), ("check_every", check_every)):
+            if not (isinstance(k, numbers.Integral) and not isinstance(k, bool) and k >= 0):
+                raise ValueError("%s: an integer >= 0, not %r" % (name, k))
+        mt = mb = None
+        if minv is not None:
+            if not (isinstance(minv, (tuple, list)) and len(minv) == 2):
+                raise TypeError("minv: a pair (top [batch, n], bottom [batch, m]) or None")
+            mt, mb = minv
+            nlp._check("minv top", mt, (nlp.batch, nlp.n))
+            nlp._check("minv bottom", mb, (nlp.batch, nlp.m))
+        top = torch.empty_like(rhs_top, memory_format=torch.contiguous_format)
+        bottom = torch.empty_like(rhs_bottom, memory_format=torch.contiguous_format)
+        iterations = torch.empty((nlp.batch,), dtype=torch.int32, device=nlp.device)
+        status = torch.empty((nlp.batch,), dtype=torch.int32, device=nlp.device)
+        residual = torch.empty((nlp.batch,), dtype=torch.float64, device=nlp.device)
+        nlp._on_current_stream(lambda s: nlp.engine.kkt_minres_device(
+            self.hess.data_ptr(), self.jac.data_ptr(), rhs_top.data_ptr(), rhs_bottom.data_ptr(), top.data_ptr(), bottom.data_ptr(), iterations.data_ptr(),
+            residual.data_ptr(), status.data_ptr(), dx_ptr=self.dx.data_ptr() if self.dx is not None else 0, dc_ptr=self.dc.data_ptr() if self.dc is not None else 0,
+            minv_top_ptr=mt.data_ptr() if mt is not None else 0, minv_bottom_ptr=mb.data_ptr() if mb is not None else 0, rtol=rtol, max_iterations=maxiter,
+            check_every=check_every, stream=s))
+        return KKTSolution(top, bottom, iterations, residual, status)
+
+
+KKTSolution = collections.namedtuple("KKTSolution", "top bottom iterations residual status")
 
 
 class _DeviceNLP:

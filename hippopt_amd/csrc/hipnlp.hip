@@ -36,6 +36,7 @@
 
 #include "knot_hess_layout.h"
 #include "knot_kkt.h"
+#include "knot_minres.h"
 #include "knot_stage.h"
 #include "layout.h"
 
@@ -1475,11 +1476,34 @@ static_assert(KK_HW + HVP_WORD_CAP / 2 <= KK_WORDS && HVP_WORD_CAP % 2 == 0, "th
 static_assert(KK_JG >= LG_ENT_CAP && JP_GLOB_CAP <= 16, "the horizon-global run of the last knot is addressed from LG_ENT_CAP on");
 static_assert(2 * ((KK_WORDS * int(sizeof(double)) + 1279) / 1280) * 1280 <= 160 * 1024, "two workgroups per CU");
 static_assert(LG_SPAN_GLOB == JP_V_STRIDE && LG_SPAN_GLOB == HVP_SPAN_GLOB, "the threads of the global columns stage the global elements of v");
-__global__ __launch_bounds__(JP_WG)
-void hipnlp_kkt_times_kernel(KktArgs a) {
+// the tree of jprod_dot_tree over a workgroup's 256 per-thread values: a butterfly over the lanes, then the four waves in order (every
+// thread returns the sum; part: four doubles of LDS, one call per launch)
+__device__ __forceinline__ double minres_tree(double acc, double* part) {
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) acc += __shfl_xor(acc, s, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return ((part[0] + part[1]) + part[2]) + part[3];
+}
+// What the MINRES apply launch (knot_minres.h) does on top of the operator: y -= (beta/oldb) r1 from the second iteration on, and the
+// knot's partial of v . y.  The operator itself instantiates the body without it: not an instruction more.
+struct KktDot {
+    const MinresRec* rec;    // [batch]: the record this iteration reads
+    const double* r1_top;    // [batch][n]
+    const double* r1_bottom; // [batch][m]
+    double* part;            // [batch][N]
+};
+template <bool DOT> __device__ __forceinline__ void kkt_times_body(const KktArgs& a, double* lds, const KktDot& d, double* tree) {
     constexpr int WG = JP_WG, JB = JP_BLOCK_CAP / WG, LQ = LG_LAM_CAP / WG, RQ = JP_ROW_CAP / WG, HB = KK_HB;
     static_assert(JP_BLOCK_CAP % WG == 0 && JP_OTHER_CAP <= WG && JP_GLOB_CAP <= WG && JP_V_STRIDE <= WG && LG_ENT_CAP == JP_BLOCK_CAP && WG == 256, "kkt staging by 256 threads");
-    __shared__ alignas(16) double lds[KK_WORDS];
+    bool sub = false;
+    double c1 = 0.0;
+    if constexpr (DOT) {
+        const MinresRec& rec = d.rec[blockIdx.y];
+        if (rec.status != MINRES_RUNNING) return;   // frozen: nothing is written
+        sub = rec.it >= 1;
+        if (sub) c1 = minres_div(rec.beta, rec.oldb);
+    }
     double* vs = lds + KK_VS;
     double* js = lds + KK_JS;
     int32_t* tw = reinterpret_cast<int32_t*>(lds + KK_TW);
@@ -1557,7 +1581,7 @@ void hipnlp_kkt_times_kernel(KktArgs a) {
 #pragma unroll
     for (int it = 0; it < RQ; ++it) {
         const bool on = ra[it] != G_NONE && with_dc;
-        wq[it] = on ? wb[ra[it] + rb[it] * k] : 0.0;
+        wq[it] = (on || (DOT && ra[it] != G_NONE)) ? wb[ra[it] + rb[it] * k] : 0.0;
         dcq[it] = on ? a.dc[int64_t(b) * a.m + ra[it] + rb[it] * k] : 0.0;
     }
     // ---- the Hessian run: the knot's block, its touch words, the coupling term of both horizon ends (held in registers across phase 1)
@@ -1592,11 +1616,16 @@ void hipnlp_kkt_times_kernel(KktArgs a) {
     if (col_thread) jtc = jprod_column_staged(false, 0.0, 0.0, e0, e1, lw, ls, js);
     else if (glob_thread) jtc = jprod_column_staged(false, 0.0, 0.0, e0, e1, lw, ls, jg - LG_ENT_CAP);
     // the owned rows of J v, and bottom
+    double yr[RQ];   // (DOT) the owned rows of y: the chain of the partial takes the top element first
     {
         double* out = a.bottom + int64_t(b) * a.m;
 #pragma unroll
         for (int it = 0; it < RQ; ++it)
-            if (ra[it] != G_NONE) out[ra[it] + rb[it] * k] = kkt_bottom(with_dc, dcq[it], wq[it], jprod_row_staged(dir[it], tw, js, vs));
+            if (ra[it] != G_NONE) {
+                double y = kkt_bottom(with_dc, dcq[it], wq[it], jprod_row_staged(dir[it], tw, js, vs));
+                if constexpr (DOT) yr[it] = y = minres_sub_r1(sub, c1, sub ? d.r1_bottom[int64_t(b) * a.m + ra[it] + rb[it] * k] : 0.0, y);
+                out[ra[it] + rb[it] * k] = y;
+            }
     }
     __syncthreads();   // every sum over the jac values is in registers: their LDS is dead
     // ---- phase 2: the Hessian block and its touch words over it
@@ -1605,11 +1634,233 @@ void hipnlp_kkt_times_kernel(KktArgs a) {
 #pragma unroll
     for (int it = 0; it < HVP_WORDS_PER_THREAD; ++it) hw[tid + it * WG] = hwr[it];
     __syncthreads();
+    double acc = 0.0;
     if (col_thread) {
         const double y = hvp_thread_row(ends_coupled ? row : row & ~(1 << HVP_COUPLED_BIT), hw, vs, [&](int pos) __attribute__((always_inline)) { return hv[pos]; }, cpl, vo);
-        a.top[int64_t(b) * a.n + int64_t(NXK) * k + tid] = kkt_top(with_dx, dxc, v0, y, jtc);
+        double t = kkt_top(with_dx, dxc, v0, y, jtc);
+        const int64_t i = int64_t(b) * a.n + int64_t(NXK) * k + tid;
+        if constexpr (DOT) { t = minres_sub_r1(sub, c1, sub ? d.r1_top[i] : 0.0, t); acc = fm_fma(v0, t, acc); }
+        a.top[i] = t;
     } else if (glob_thread) {   // no entry of the Hessian touches the horizon-global variables
-        a.top[int64_t(b) * a.n + int64_t(NXK) * N + (tid - LG_SPAN_GLOB)] = kkt_top(with_dx, dxc, v0, 0.0, jtc);
+        double t = kkt_top(with_dx, dxc, v0, 0.0, jtc);
+        const int64_t i = int64_t(b) * a.n + int64_t(NXK) * N + (tid - LG_SPAN_GLOB);
+        if constexpr (DOT) { t = minres_sub_r1(sub, c1, sub ? d.r1_top[i] : 0.0, t); acc = fm_fma(v0, t, acc); }
+        a.top[i] = t;
+    }
+    if constexpr (DOT) {   // the knot's partial of v . y: top element, first row, second row; then the tree of jprod_dot_tree
+#pragma unroll
+        for (int it = 0; it < RQ; ++it)
+            if (ra[it] != G_NONE) acc = fm_fma(wq[it], yr[it], acc);
+        const double s = minres_tree(acc, tree);
+        if (tid == 0) d.part[int64_t(b) * N + k] = s;
+    }
+}
+__global__ __launch_bounds__(JP_WG)
+void hipnlp_kkt_times_kernel(KktArgs a) {
+    __shared__ alignas(16) double lds[KK_WORDS];
+    kkt_times_body<false>(a, lds, KktDot(), nullptr);
+}
+
+
+// =====================================================================================================================
+// Preconditioned MINRES on that operator (hipnlp_kkt_minres_device; knot_minres.h has the recurrence, the launch structure and the order
+// of every sum).  Three launches per iteration on the operator's grid, every reduction across a launch boundary; no workgroup waits for
+// another, no atomics.  The workspace: MR_VECS vectors, each [batch][n] then [batch][m]; two runs of per-knot partials [batch][N]; two
+// buffers of scalar records [batch], read and written by iteration parity.
+// =====================================================================================================================
+struct MinresArgs {
+    const JprodTables* jt;
+    const double* minv_top;      // [batch][n] or null (with minv_bottom)
+    const double* minv_bottom;   // [batch][m]
+    const double* rhs_top;       // [batch][n]
+    const double* rhs_bottom;    // [batch][m]
+    double* z_top;               // [batch][n]
+    double* z_bottom;            // [batch][m]
+    double* vec;                 // [MR_VECS][batch (n + m)]
+    double* part_a;              // [batch][N]: v . y
+    double* part_b;              // [batch][N]: r2 . M^-1 r2
+    MinresRec* rec;              // [2][batch]
+    int32_t* iterations;         // [batch]
+    double* residual;            // [batch]
+    int32_t* status;             // [batch]
+    double rtol;
+    int32_t N, n, m, batch, maxit;
+    int32_t it;                  // the iteration these launches belong to (0: the start)
+    __device__ __forceinline__ double* top(int v, int b) const { return vec + int64_t(v) * batch * (int64_t(n) + m) + int64_t(b) * n; }
+    __device__ __forceinline__ double* bottom(int v, int b) const { return vec + int64_t(v) * batch * (int64_t(n) + m) + int64_t(batch) * n + int64_t(b) * m; }
+    __device__ __forceinline__ const MinresRec& rec_in(int b) const { return rec[int64_t((it - 1) & 1) * batch + b]; }
+    __device__ __forceinline__ MinresRec& rec_out(int b) const { return rec[int64_t(it & 1) * batch + b]; }
+};
+// minres_sum for a whole workgroup — K runs of N per-knot partials, each from +0.0 in ascending knot order, every thread returning the same
+// bits.  The chain of additions is the order the header fixes and stays serial, but only the first wave walks it, and off registers: its
+// lanes load up to 256 addends per run in ONE memory round trip, the chain takes them lane by lane (v_readlane), the other waves get the
+// sums through LDS.  (Left to every thread over global memory the chain pays a memory round trip per addend.)  buf: K doubles.
+__device__ __forceinline__ double minres_readlane(double x, int lane) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), lane), __builtin_amdgcn_readlane(__double2loint(x), lane));
+}
+template <int K> __device__ __forceinline__ void minres_sum_staged(const double* const (&part)[K], int N, double* buf, double (&sum)[K]) {
+    if (threadIdx.x < 64) {
+        const int lane = threadIdx.x;
+        double acc[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) acc[j] = 0.0;
+        for (int base = 0; base < N; base += 256) {
+            double x[K][4];
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) { const int i = base + 64 * c + lane; x[j][c] = i < N ? part[j][i] : 0.0; }
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int left = N - base - 64 * c, cnt = left < 64 ? left : 64;
+                for (int i = 0; i < cnt; ++i) {
+#pragma unroll
+                    for (int j = 0; j < K; ++j) acc[j] += minres_readlane(x[j][c], i);
+                }
+            }
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) buf[j] = acc[j];
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < K; ++j) sum[j] = buf[j];
+}
+__device__ __forceinline__ MinresOwned minres_owned_of(const MinresArgs& s, int tid, int k) {
+    const int pv = k == 0 ? PV_FIRST : (k == s.N - 1 ? PV_LAST : (k == 1 ? PV_SECOND : PV_INTERIOR));
+    return minres_owned(tid, k, s.N, s.jt->row_a[pv], s.jt->row_b[pv]);
+}
+
+__global__ __launch_bounds__(JP_WG)
+void hipnlp_kkt_minres_apply_kernel(KktArgs a, MinresArgs s) {
+    __shared__ alignas(16) double lds[KK_WORDS];
+    __shared__ double tree[JP_WG / 64];
+    KktDot d;
+    d.rec = &s.rec_in(0); d.r1_top = s.top(MR_R1, 0); d.r1_bottom = s.bottom(MR_R1, 0); d.part = s.part_a;
+    kkt_times_body<true>(a, lds, d, tree);
+}
+static_assert(2 * ((KK_WORDS * int(sizeof(double)) + JP_WG / 64 * int(sizeof(double)) + 1279) / 1280) * 1280 <= 160 * 1024, "apply: two workgroups per CU");
+
+// first update (it >= 1): y -= (alfa/beta) r2;  r1 = r2;  r2 = y;  y = M^-1 r2;  the knot's partial of r2 . y.
+// the start (it == 0):    r1 = r2 = b;  y = M^-1 r2;  w = w2 = 0;  z = 0;  the same partial.
+__global__ __launch_bounds__(JP_WG)
+void hipnlp_kkt_minres_first_kernel(MinresArgs s) {
+    __shared__ double tree[JP_WG / 64];
+    __shared__ double buf[1];
+    const int tid = threadIdx.x, b = blockIdx.y, k = blockIdx.x;
+    const bool init = s.it == 0, with_minv = s.minv_top != nullptr;
+    if (!init && s.rec_in(b).status != MINRES_RUNNING) return;
+    // everything the elements need is requested before the chain of the sum: one memory round trip for the tables, one for the data
+    const MinresOwned o = minres_owned_of(s, tid, k);
+    const int32_t e[3] = {o.top, o.row[0], o.row[1]};
+    double in_y[3], in_r2[3], in_m[3];   // (the start: in_y is b)
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const bool on = e[q] >= 0;
+        const int64_t i = (q == 0 ? int64_t(b) * s.n : int64_t(b) * s.m) + (on ? e[q] : 0);
+        const double* y = init ? (q == 0 ? s.rhs_top : s.rhs_bottom) : (q == 0 ? s.top(MR_Y, 0) : s.bottom(MR_Y, 0));
+        in_y[q] = on ? y[i] : 0.0;
+        in_r2[q] = (on && !init) ? (q == 0 ? s.top(MR_R2, 0) : s.bottom(MR_R2, 0))[i] : 0.0;
+        in_m[q] = (on && with_minv) ? (q == 0 ? s.minv_top : s.minv_bottom)[i] : 0.0;
+    }
+    double c2 = 0.0;
+    if (!init) {
+        const double* const part[1] = {s.part_a + int64_t(b) * s.N};
+        double alfa[1];
+        minres_sum_staged<1>(part, s.N, buf, alfa);
+        c2 = minres_div(alfa[0], s.rec_in(b).beta);
+    }
+    double acc = 0.0;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        if (e[q] < 0) continue;
+        const int64_t i = (q == 0 ? int64_t(b) * s.n : int64_t(b) * s.m) + e[q];
+        auto vec = [&](int v) __attribute__((always_inline)) { return q == 0 ? s.top(v, 0) : s.bottom(v, 0); };
+        double r;
+        if (init) {
+            r = in_y[q];
+            vec(MR_W)[i] = 0.0; vec(MR_W2)[i] = 0.0; (q == 0 ? s.z_top : s.z_bottom)[i] = 0.0;
+            vec(MR_R1)[i] = r;
+        } else {
+            r = minres_new_r2(c2, in_r2[q], in_y[q]);
+            vec(MR_R1)[i] = in_r2[q];
+        }
+        vec(MR_R2)[i] = r;
+        const double ym = minres_precond(with_minv, in_m[q], r);
+        vec(MR_Y)[i] = ym;
+        acc = fm_fma(r, ym, acc);
+    }
+    const double sum = minres_tree(acc, tree);
+    if (tid == 0) s.part_b[int64_t(b) * s.N + k] = sum;
+}
+
+// second update (it >= 1): the scalar step; w1 = w2; w2 = w; w = (v - oldeps w1 - delta w2)/gamma; z += phi w; the next v = y / beta.
+// the start (it == 0):     the initial record; the first v = y / beta1.
+// The workgroup of knot 0 writes the record of the other parity and the trajectory's iterations, residual and status.
+__global__ __launch_bounds__(JP_WG)
+void hipnlp_kkt_minres_second_kernel(MinresArgs s) {
+    __shared__ double buf[2];
+    const int tid = threadIdx.x, b = blockIdx.y, k = blockIdx.x;
+    const bool init = s.it == 0;
+    MinresRec in;
+    if (!init) {
+        in = s.rec_in(b);
+        if (in.status != MINRES_RUNNING) {   // frozen: the record moves to the other buffer bit for bit, nothing else is written
+            if (k == 0 && tid == 0) s.rec_out(b) = in;
+            return;
+        }
+    }
+    // the elements' inputs are requested before the chains of the sums
+    const MinresOwned o = minres_owned_of(s, tid, k);
+    const int32_t e[3] = {o.top, o.row[0], o.row[1]};
+    double in_v[3], in_y[3], in_w[3], in_w2[3], in_z[3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const bool on = e[q] >= 0;
+        const int64_t i = (q == 0 ? int64_t(b) * s.n : int64_t(b) * s.m) + (on ? e[q] : 0);
+        auto vec = [&](int v) __attribute__((always_inline)) { return q == 0 ? s.top(v, 0) : s.bottom(v, 0); };
+        in_y[q] = on ? vec(MR_Y)[i] : 0.0;
+        in_v[q] = (on && !init) ? vec(MR_V)[i] : 0.0;
+        in_w[q] = (on && !init) ? vec(MR_W)[i] : 0.0;
+        in_w2[q] = (on && !init) ? vec(MR_W2)[i] : 0.0;
+        in_z[q] = (on && !init) ? (q == 0 ? s.z_top : s.z_bottom)[i] : 0.0;
+    }
+    MinresRec rec;
+    MinresStep st = {0.0, 0.0, 0.0, 0.0};
+    bool update = false;
+    const double* const part[2] = {s.part_a + int64_t(b) * s.N, s.part_b + int64_t(b) * s.N};
+    if (init) {
+        const double* const only[1] = {part[1]};
+        double one[1];
+        minres_sum_staged<1>(only, s.N, buf, one);
+        rec = minres_init(one[0], s.rtol, s.maxit);
+    } else {
+        double sum[2];
+        minres_sum_staged<2>(part, s.N, buf, sum);
+        rec = minres_step(in, sum[0], sum[1], s.rtol, s.maxit, st);
+        update = rec.status != MINRES_BREAKDOWN;
+    }
+    if (k == 0 && tid == 0) {
+        s.rec_out(b) = rec;
+        s.iterations[b] = rec.it;
+        s.residual[b] = rec.residual;
+        s.status[b] = rec.status;
+    }
+    const bool next = rec.status == MINRES_RUNNING;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        if (e[q] < 0) continue;
+        const int64_t i = (q == 0 ? int64_t(b) * s.n : int64_t(b) * s.m) + e[q];
+        auto vec = [&](int v) __attribute__((always_inline)) { return q == 0 ? s.top(v, 0) : s.bottom(v, 0); };
+        if (update) {
+            const double wn = minres_new_w(st, in_v[q], in_w2[q], in_w[q]);
+            vec(MR_W2)[i] = in_w[q];
+            vec(MR_W)[i] = wn;
+            (q == 0 ? s.z_top : s.z_bottom)[i] = minres_new_z(st, wn, in_z[q]);
+        }
+        if (next) vec(MR_V)[i] = minres_div(in_y[q], rec.beta);
     }
 }
 
@@ -1881,6 +2132,8 @@ struct hipnlp_handle {
     JprodTables* d_jt = nullptr;
     LgradTables* d_jtt = nullptr;
     double* d_jdot = nullptr;
+    double* d_minres = nullptr;          // the workspace of hipnlp_kkt_minres_device: vectors, partials, scalar records (one allocation)
+    int32_t* h_minres_status = nullptr;  // pinned [batch]: the statuses a check_every > 0 solve looks at
     std::string err;
 };
 
@@ -1935,9 +2188,9 @@ static void free_all(hipnlp_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->dev);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* dptrs[] = {h->d_tb, h->d_ctpl, h->d_ctpl_of_b, h->d_healed, h->d_x, h->d_pk, h->d_cost_knot, h->d_gp, h->d_cost_pub, h->d_out, h->d_ht, h->d_sigma, h->d_hess, h->d_hflag, h->d_htrash, h->d_lt, h->d_vt, h->d_jt, h->d_jtt, h->d_jdot};
+    void* dptrs[] = {h->d_tb, h->d_ctpl, h->d_ctpl_of_b, h->d_healed, h->d_x, h->d_pk, h->d_cost_knot, h->d_gp, h->d_cost_pub, h->d_out, h->d_ht, h->d_sigma, h->d_hess, h->d_hflag, h->d_htrash, h->d_lt, h->d_vt, h->d_jt, h->d_jtt, h->d_jdot, h->d_minres};
     for (void* q : dptrs) if (q) (void)hipFree(q);
-    void* hptrs[] = {h->h_x, h->h_out, h->h_hess, h->h_hflag, h->h_sl};
+    void* hptrs[] = {h->h_x, h->h_out, h->h_hess, h->h_hflag, h->h_sl, h->h_minres_status};
     for (void* q : hptrs) if (q) (void)hipHostFree(q);
     for (hipEvent_t e : h->prof_ev) (void)hipEventDestroy(e);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -3317,6 +3570,79 @@ int hipnlp_kkt_times_device(hipnlp_handle* h, const double* hess_values_dev, con
     a.nnz = L.nnz; a.glob_base = L.jac_glob_base; a.nnz_h = hess_count(h);
     hipLaunchKernelGGL(hipnlp_kkt_times_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(JP_WG), 0, stream ? hipStream_t(stream) : h->stream, a);
     HIP_TRY(h, hipGetLastError());
+    return HIPNLP_OK;
+}
+// ---- MINRES on the KKT operator (include/hipnlp.h; knot_minres.h) ------------------------------------------------------------------------
+static size_t minres_align(size_t bytes) { return (bytes + 255) / 256 * 256; }
+static size_t minres_vec_bytes(const hipnlp_handle* h) { return minres_align(size_t(MR_VECS) * size_t(h->batch) * (size_t(h->L.n) + size_t(h->L.m)) * sizeof(double)); }
+static size_t minres_part_bytes(const hipnlp_handle* h) { return minres_align(size_t(h->batch) * size_t(h->L.N) * sizeof(double)); }
+static size_t minres_bytes(const hipnlp_handle* h) { return minres_vec_bytes(h) + 2 * minres_part_bytes(h) + minres_align(2 * size_t(h->batch) * sizeof(MinresRec)); }
+static int minres_prepare(hipnlp_handle* h, const char* who) {
+    if (h->is_front) { h->err = std::string(who) + ": a multi-device handle (hipnlp_multi_create) serves the host-buffer calls only"; return HIPNLP_E_UNSUPPORTED; }
+    if (const int rc = whole_horizon_only(h, who, "a row of g has entries in the blocks of two knots, the periodicity coupling needs both horizon ends")) return rc;
+    if (!h->L.lgrad_ok) { h->err = std::string(who) + ": " + h->L.lgrad_error; return HIPNLP_E_UNSUPPORTED; }
+    if (const int rc = jprod_prepare(h, who)) return rc;
+    if (const int rc = hvp_prepare(h, who)) return rc;
+    HIP_TRY(h, hipSetDevice(h->dev));
+    if (!h->d_minres) HIP_TRY(h, hipMalloc(&h->d_minres, minres_bytes(h)));
+    if (!h->h_minres_status) HIP_TRY(h, hipHostMalloc(&h->h_minres_status, size_t(h->batch) * sizeof(int32_t)));
+    return HIPNLP_OK;
+}
+int hipnlp_kkt_minres_reserve(hipnlp_handle* h, int64_t* bytes_out) {
+    if (!h) return HIPNLP_E_INVALID;
+    if (const int rc = minres_prepare(h, "hipnlp_kkt_minres_reserve")) return rc;
+    if (bytes_out) *bytes_out = int64_t(minres_bytes(h));
+    return HIPNLP_OK;
+}
+int hipnlp_kkt_minres_device(hipnlp_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev, const double* dc_dev,
+                             const double* minv_top_dev, const double* minv_bottom_dev, const double* rhs_top_dev, const double* rhs_bottom_dev, double* sol_top_dev,
+                             double* sol_bottom_dev, double rtol, int max_iterations, int check_every, int32_t* iterations_dev, double* residual_dev, int32_t* status_dev,
+                             void* stream) {
+    if (!h || !hess_values_dev || !jac_values_dev || !rhs_top_dev || !rhs_bottom_dev || !sol_top_dev || !sol_bottom_dev || !iterations_dev || !residual_dev || !status_dev)
+        return HIPNLP_E_INVALID;
+    if (!(rtol >= 0.0) || max_iterations < 0 || check_every < 0 || (minv_top_dev == nullptr) != (minv_bottom_dev == nullptr)) {
+        h->err = "hipnlp_kkt_minres_device: rtol >= 0, max_iterations >= 0, check_every >= 0, and both or neither of minv_top_dev / minv_bottom_dev";
+        return HIPNLP_E_INVALID;
+    }
+    if (const int rc = minres_prepare(h, "hipnlp_kkt_minres_device")) return rc;
+    hipStream_t st = stream ? hipStream_t(stream) : h->stream;
+    const Layout& L = h->L;
+    MinresArgs s;
+    s.jt = h->d_jt; s.minv_top = minv_top_dev; s.minv_bottom = minv_bottom_dev; s.rhs_top = rhs_top_dev; s.rhs_bottom = rhs_bottom_dev;
+    s.z_top = sol_top_dev; s.z_bottom = sol_bottom_dev;
+    char* base = reinterpret_cast<char*>(h->d_minres);
+    s.vec = reinterpret_cast<double*>(base);
+    s.part_a = reinterpret_cast<double*>(base + minres_vec_bytes(h));
+    s.part_b = reinterpret_cast<double*>(base + minres_vec_bytes(h) + minres_part_bytes(h));
+    s.rec = reinterpret_cast<MinresRec*>(base + minres_vec_bytes(h) + 2 * minres_part_bytes(h));
+    s.iterations = iterations_dev; s.residual = residual_dev; s.status = status_dev;
+    s.rtol = rtol; s.N = L.N; s.n = L.n; s.m = L.m; s.batch = h->batch; s.maxit = max_iterations; s.it = 0;
+    KktArgs a;
+    a.jt = h->d_jt; a.tt = h->d_jtt; a.vt = h->d_vt; a.hvals = hess_values_dev; a.jvals = jac_values_dev; a.dx = dx_dev; a.dc = dc_dev;
+    a.v = s.vec + int64_t(MR_V) * h->batch * (int64_t(L.n) + L.m); a.w = a.v + int64_t(h->batch) * L.n;
+    a.top = s.vec + int64_t(MR_Y) * h->batch * (int64_t(L.n) + L.m); a.bottom = a.top + int64_t(h->batch) * L.n;
+    a.N = L.N; a.n = L.n; a.m = L.m;
+    a.nnz_first = L.nnz_v[VAR_FIRST]; a.nnz_interior = L.nnz_v[VAR_INTERIOR]; a.nnz_last = L.nnz_v[VAR_LAST]; a.nnz_glob = int32_t(L.jperm_glob.size());
+    a.nnz_knot = h->HL.nnz_knot; a.n_couple = h->HL.n_couple;
+    a.nnz = L.nnz; a.glob_base = L.jac_glob_base; a.nnz_h = hess_count(h);
+    const dim3 grid(unsigned(h->nk), unsigned(h->batch)), wg(JP_WG);
+    hipLaunchKernelGGL(hipnlp_kkt_minres_first_kernel, grid, wg, 0, st, s);
+    hipLaunchKernelGGL(hipnlp_kkt_minres_second_kernel, grid, wg, 0, st, s);
+    HIP_TRY(h, hipGetLastError());
+    for (int it = 1; it <= max_iterations; ++it) {
+        s.it = it;
+        hipLaunchKernelGGL(hipnlp_kkt_minres_apply_kernel, grid, wg, 0, st, a, s);
+        hipLaunchKernelGGL(hipnlp_kkt_minres_first_kernel, grid, wg, 0, st, s);
+        hipLaunchKernelGGL(hipnlp_kkt_minres_second_kernel, grid, wg, 0, st, s);
+        HIP_TRY(h, hipGetLastError());
+        if (check_every > 0 && it % check_every == 0 && it < max_iterations) {   // the only synchronisation: is any trajectory still running?
+            HIP_TRY(h, hipMemcpyAsync(h->h_minres_status, status_dev, size_t(h->batch) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipStreamSynchronize(st));
+            bool running = false;
+            for (int b = 0; b < h->batch; ++b) running = running || h->h_minres_status[b] == MINRES_RUNNING;
+            if (!running) break;
+        }
+    }
     return HIPNLP_OK;
 }
 // how a handle in auto mode (hipnlp_set_hessian_early_run(h, -1)) came to its choice

@@ -28,7 +28,7 @@ EXPORTS = [
     "hipnlp_device_numa_node", "hipnlp_pin_thread_to_device_numa_node",
     "hipnlp_hess_nnz", "hipnlp_hess_sparsity", "hipnlp_eval_hess", "hipnlp_eval_hess_at", "hipnlp_set_hessian_early_run", "hipnlp_get_hessian_early_run", "hipnlp_hessian_early_run_reason", "hipnlp_eval_hess_device",
     "hipnlp_eval_lagrangian_grad_device", "hipnlp_eval_hess_vec_device", "hipnlp_hess_times_device",
-    "hipnlp_jac_times_device", "hipnlp_jac_transpose_times_device", "hipnlp_kkt_times_device",
+    "hipnlp_jac_times_device", "hipnlp_jac_transpose_times_device", "hipnlp_kkt_times_device", "hipnlp_kkt_minres_device", "hipnlp_kkt_minres_reserve",
     "hipnlp_eval_pinned", "hipnlp_set_prefetch", "hipnlp_set_early_outputs", "hipnlp_set_host_timing", "hipnlp_host_register", "hipnlp_host_unregister",
     "hipnlp_multi_create", "hipnlp_multi_plan", "hipnlp_multi_info", "hipnlp_multi_breakdown", "hipnlp_multi_set_threads",
     "hipnlp_host_breakdown", "hipnlp_set_auto_register", "hipnlp_host_stats", "hipnlp_set_constant_jacobian", "hipnlp_forget_jac_destination", "hipnlp_jac_constant_mask", "hipnlp_host_release_auto_ranges",
@@ -222,6 +222,9 @@ def load_library(path=None):
         lib.hipnlp_jac_transpose_times_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     if hasattr(lib, "hipnlp_kkt_times_device"):
         lib.hipnlp_kkt_times_device.argtypes = [vp] * 10
+    if hasattr(lib, "hipnlp_kkt_minres_device"):
+        lib.hipnlp_kkt_minres_device.argtypes = [vp] * 11 + [C.c_double, C.c_int, C.c_int] + [vp] * 4
+        lib.hipnlp_kkt_minres_reserve.argtypes = [vp, C.POINTER(C.c_int64)]
     _libs[path] = lib
     return lib
 
@@ -624,6 +627,26 @@ class HipNlp:
         vp = C.c_void_p
         self._check(self.lib.hipnlp_kkt_times_device(self.h, vp(hess_values_ptr or None), vp(jac_values_ptr or None), vp(dx_ptr or None), vp(dc_ptr or None),
                                                      vp(v_ptr or None), vp(w_ptr or None), vp(top_ptr or None), vp(bottom_ptr or None), vp(stream or None)))
+
+    def kkt_minres_device(self, hess_values_ptr, jac_values_ptr, rhs_top_ptr, rhs_bottom_ptr, sol_top_ptr, sol_bottom_ptr, iterations_ptr, residual_ptr, status_ptr,
+                          dx_ptr=0, dc_ptr=0, minv_top_ptr=0, minv_bottom_ptr=0, rtol=1e-8, max_iterations=200, check_every=16, stream=0):
+        """Preconditioned MINRES on the KKT operator of kkt_times_device for every trajectory at once (hipnlp_kkt_minres_device), from a
+        zero start: sol [batch][n] / [batch][m], iterations and status (int32) and residual [batch] are device pointers; the
+        preconditioner diag(minv_top, minv_bottom) > 0 is optional (both 0: the identity).  Status 0 converged, 1 iteration limit, 2
+        breakdown.  check_every == 0 enqueues max_iterations iterations and never synchronises; k > 0 waits for the stream after every k
+        iterations and stops once no trajectory is still running — the same bits either way.  Solves on one handle share its workspace:
+        order them on one stream."""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_kkt_minres_device(self.h, vp(hess_values_ptr or None), vp(jac_values_ptr or None), vp(dx_ptr or None), vp(dc_ptr or None),
+                                                      vp(minv_top_ptr or None), vp(minv_bottom_ptr or None), vp(rhs_top_ptr or None), vp(rhs_bottom_ptr or None),
+                                                      vp(sol_top_ptr or None), vp(sol_bottom_ptr or None), float(rtol), int(max_iterations), int(check_every),
+                                                      vp(iterations_ptr or None), vp(residual_ptr or None), vp(status_ptr or None), vp(stream or None)))
+
+    def kkt_minres_reserve(self):
+        """allocate the handle's MINRES workspace now (otherwise: on the first solve); returns its size in bytes"""
+        nbytes = C.c_int64(0)
+        self._check(self.lib.hipnlp_kkt_minres_reserve(self.h, C.byref(nbytes)))
+        return nbytes.value
 
     def cost_terms(self):
         out = np.empty((self.batch, _abi.NCOST_TERMS))

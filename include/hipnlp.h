@@ -506,6 +506,53 @@ int hipnlp_kkt_times_device(hipnlp_handle* h, const double* hess_values_dev, con
                             const double* dc_dev, const double* v_dev, const double* w_dev, double* top_dev, double* bottom_dev,
                             void* stream);
 
+/* Preconditioned MINRES (Paige and Saunders) on that operator, for every trajectory of the batch at once, resident on the device:
+ *
+ *     K [sol_top; sol_bottom] = [rhs_top; rhs_bottom],   K = [[H + diag d_x, J^T], [J, -diag d_c]]
+ *
+ * from the two value runs and the diagonals of hipnlp_kkt_times_device (same rules).  The start is zero (a caller who wants a warm start
+ * solves for the correction).  The preconditioner M^-1 = diag(minv_top_dev [batch][n], minv_bottom_dev [batch][m]) > 0 is the caller's;
+ * both NULL: the identity, nothing is read.  Building a preconditioner is not part of the library.  rhs_top_dev, sol_top_dev [batch][n];
+ * rhs_bottom_dev, sol_bottom_dev [batch][m]; iterations_dev, status_dev (int32) and residual_dev [batch].  residual is phibar / beta1:
+ * the relative residual in the M^-1 norm, sqrt(r . M^-1 r) / sqrt(b . M^-1 b), as the recurrence estimates it.
+ *
+ * Status per trajectory: 0 converged, phibar <= rtol beta1 (this includes rhs = 0: zero iterations, sol = 0);  1 the iteration limit;
+ * 2 breakdown: r . M^-1 r < 0 or a non-finite alfa, beta or gamma — M is not positive definite or the data is not finite; the trajectory
+ * stops with the last finite sol (at the start: sol = 0, residual 1).  Once a trajectory has a final status it is FROZEN: the launches
+ * that follow leave its vectors, scalars, sol, iterations, residual and status bit for bit as they are.
+ *
+ * Launches (knot_minres.h has the recurrence and every expression): two for the start, three per iteration, all on the grid
+ * (knots, batch) of the operator.  No workgroup waits for another, no atomics, no persistent kernel: every reduction over a trajectory
+ * crosses a launch boundary, and the scalars of the recurrence never visit the host (two records per trajectory, read and written by
+ * iteration parity).  Order of every sum: y = K v exactly as hipnlp_kkt_times_device sums it, then y -= (beta/oldb) r1 by one fused
+ * multiply-add per element;  a dot product is, per knot, ONE chain of fused multiply-adds per thread from +0.0 over the elements the
+ * knot's workgroup of the operator writes (its element of the top, then its first, then its second row), the tree of the grad f . v
+ * partial of hipnlp_jac_times_device over the 256 threads, and then the N per-knot partials from +0.0 in ascending knot order, added
+ * by every workgroup of the next launch for itself (at every N: there is no reduce launch).  Divisions and square roots are correctly
+ * rounded.  So the same bits at every position of a batch, for both jac orders, and for every check_every.
+ *
+ * check_every == 0: exactly max_iterations iterations are enqueued on `stream` and the call never synchronises (frozen trajectories
+ * make the surplus a no-op).  check_every == k > 0: after every k iterations the [batch] statuses are copied into a pinned block of the
+ * handle and the stream is waited for; enqueuing stops once no trajectory is still running.  That copy and wait is the only
+ * synchronisation, and check_every changes no output bit.  (A call with check_every > 0 cannot be captured into a graph.)
+ *
+ * The workspace — six vectors of n + m per trajectory (v, y, r1, r2, w, w2; w1 of the recurrence needs no storage), two runs of per-knot
+ * partials and the scalar records — belongs to the handle: allocated by hipnlp_kkt_minres_reserve (bytes_out, optional: its size) or by
+ * the first solve, freed with the handle.  It is ONE per handle: solves on one handle must be ordered on one stream (or by the
+ * caller's events).  The outputs may not alias the inputs; nothing but the six outputs and the workspace is written.
+ *
+ * NOT claimed: convergence on the KKT systems of real iterates — they are indefinite and badly scaled (entries reach 1e8 on the stairs
+ * terrain) and no preconditioner is built here; the tests converge on conditioned synthetic value runs only.
+ *
+ * Returns as hipnlp_kkt_times_device (HIPNLP_E_INVALID for a missing handle or required pointer — all but dx_dev, dc_dev and the two
+ * minv; HIPNLP_E_UNSUPPORTED on a multi-device handle, a shard handle, a layout beyond the caps), and HIPNLP_E_INVALID for rtol < 0,
+ * max_iterations < 0, check_every < 0 and for exactly one of the two minv pointers. */
+int hipnlp_kkt_minres_device(hipnlp_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev,
+                             const double* dc_dev, const double* minv_top_dev, const double* minv_bottom_dev, const double* rhs_top_dev,
+                             const double* rhs_bottom_dev, double* sol_top_dev, double* sol_bottom_dev, double rtol, int max_iterations,
+                             int check_every, int32_t* iterations_dev, double* residual_dev, int32_t* status_dev, void* stream);
+int hipnlp_kkt_minres_reserve(hipnlp_handle* h, int64_t* bytes_out);
+
 /* Sharded variant (multi-GPU): the handle owns knots [knot_begin, knot_end).  Outputs are
  * shard-local and contiguous so that one RCCL all-gather reassembles them:
  *   grad_shard [batch][shard_grad]  = grad f entries of the shard's knots (+ the 6 global entries on the last shard)
