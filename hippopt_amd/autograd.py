@@ -20,6 +20,7 @@
     top, bottom = K.matvec(v, w)                           # (H + diag dx) v + J^T w [B, n] and J v - dc w [B, m], ONE launch (hipnlp_kkt_times_device)
     K2 = K.with_diagonals(dx2, dc2)                        # other diagonals on the same value runs: no launch
     z = K.solve(b_top, b_bottom, rtol=1e-8, maxiter=200)   # K [z.top; z.bottom] = b by MINRES on the device (hipnlp_kkt_minres_device); z.status
+    z = K.solve(b_top, b_bottom, minv=K.diagonal_preconditioner())   # ... with the diagonal M^-1 built in ONE launch (hipnlp_kkt_diag_precond_device)
 
 The forward pass is hipnlp_eval_device with grad f and jac g left out; the backward pass is the Lagrangian gradient
 sigma grad f + J^T lambda with sigma = df, lambda = dg (zeros for an output whose gradient is None): the Jacobian never reaches memory.
@@ -262,6 +263,23 @@ class KKTValues:
                                                                      dc_ptr=self.dc.data_ptr() if self.dc is not None else 0, stream=s))
         return top, bottom
 
+    def diagonal_preconditioner(self, floor=1e-10):
+        """(top [batch, n], bottom [batch, m]), ready for solve(minv=...): top = 1 / max(|diag H + dx|, floor) and
+        bottom = 1 / max(|dc + sum_e J_ie^2 top_col(e)|, floor), built on the device in ONE launch (hipnlp_kkt_diag_precond_device) from
+        this operator's own value runs and diagonals — K.with_diagonals(dx, dc).diagonal_preconditioner() is the one that matches other
+        diagonals.  The absolute value keeps M positive definite where H + diag dx is not.  floor > 0 keeps the reciprocals finite; its
+        default is a guess nobody has tuned.  A NaN or an infinity in the value runs or diagonals comes out as NaN (solve: status 2).
+        What it was measured to do: solve's docstring."""
+        torch, nlp = _torch(), self.nlp
+        if not (isinstance(floor, numbers.Real) and not isinstance(floor, bool) and 0.0 < floor < float("inf")):
+            raise ValueError("floor: a finite real number > 0, not %r" % (floor,))
+        top = torch.empty((nlp.batch, nlp.n), dtype=torch.float64, device=self.hess.device)
+        bottom = torch.empty((nlp.batch, nlp.m), dtype=torch.float64, device=self.hess.device)
+        nlp._on_current_stream(lambda s: nlp.engine.kkt_diag_precond_device(self.hess.data_ptr(), self.jac.data_ptr(), top.data_ptr(), bottom.data_ptr(),
+                                                                            dx_ptr=self.dx.data_ptr() if self.dx is not None else 0,
+                                                                            dc_ptr=self.dc.data_ptr() if self.dc is not None else 0, floor=float(floor), stream=s))
+        return top, bottom
+
     def solve(self, rhs_top, rhs_bottom, rtol=1e-8, maxiter=200, minv=None, check_every=16):
         """KKTSolution(top [batch, n], bottom [batch, m], iterations [batch] int32, residual [batch], status [batch] int32) of
         K [top; bottom] = [rhs_top; rhs_bottom] by preconditioned MINRES from a zero start, resident on the device
@@ -271,7 +289,12 @@ class KKTValues:
         waits for the stream after every k iterations and stops once every trajectory has a status; 0 enqueues maxiter iterations
         without ever waiting — the same bits.  The solves of one nlp share a workspace: keep them on one stream.  Not recorded by
         autograd: a right-hand side that requires grad gets a solution without a graph.  No convergence is promised on the KKT systems of
-        real iterates (indefinite, badly scaled; no preconditioner is built here)."""
+        real iterates (indefinite, badly scaled).  minv=self.diagonal_preconditioner() is the one preconditioner built here; measured with
+        it (rtol 1e-8, the CPU emulation of these launches, dx and dc in U[1, 2] — not an interior-point method's): symmetrically
+        rescaled synthetic systems K' = S K S with cond 1e12 converge in the 23 to 25 iterations of the unscaled system where the
+        identity stands at a residual of 4e-2 after 300; on the real N = 4 value runs of the stairs terrain (cond 3e9) status 0 after
+        2194 iterations where the identity has residual 0.47 after 3000, on the planar terrain about a fifth fewer iterations than the
+        identity's 2123.  That does not make an interior-point step cheap; larger systems: profiles/r13_kkt_precond.txt."""
         torch, nlp = _torch(), self.nlp
         nlp._check("rhs_top", rhs_top, (nlp.batch, nlp.n))
         nlp._check("rhs_bottom", rhs_bottom, (nlp.batch, nlp.m))

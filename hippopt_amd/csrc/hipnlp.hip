@@ -36,6 +36,7 @@
 
 #include "knot_hess_layout.h"
 #include "knot_kkt.h"
+#include "knot_kkt_precond.h"
 #include "knot_minres.h"
 #include "knot_stage.h"
 #include "layout.h"
@@ -1865,6 +1866,136 @@ void hipnlp_kkt_minres_second_kernel(MinresArgs s) {
 }
 
 
+// =====================================================================================================================
+// The diagonal preconditioner of that solve from the same stored value runs (hipnlp_kkt_diag_precond_device; knot_kkt_precond.h has the
+// expressions and their rounding):
+//     minv_top_j = 1 / max(|H_jj + d_x,j|, floor),     minv_bottom_i = 1 / max(|d_c,i + sum_e J_ie^2 minv_top_col(e)|, floor)
+// ONE launch on the operator's grid, one workgroup per (trajectory, knot).  No knot program, no atomics, no exchange between workgroups:
+// a row of g owned by knot k has its columns in the records of knot k, of its predecessor, of the other horizon end (the last knot's
+// periodicity rows) and among the six globals, and the workgroup computes minv_top of all four records ITSELF — one gathered Hessian
+// value (SaddleDiagTables::diag, the block position of the variable's diagonal entry) and one d_x per thread and record; the same
+// expression on the same inputs as the owner's, so the same bits.  The Hessian block is not staged.
+//   loads: everything is requested before the first LDS write: the own and the predecessor's block of the jac run and the extras, as
+//   phase 1 of the operator; the row entry words; the diagonal entries and d_x of the records; d_c of the owned rows.
+//   LDS: the four records of minv_top in the JP_V_* arrangement (where the operator keeps v), the jac values, the row entry words:
+//   42 688 B — three workgroups per CU by LDS (34 granules of 1 280 B each).
+//   behind the one barrier: the owned rows over the JprodTables words (precond_row_staged), d_c last, the reciprocal.
+// Writes follow minres_owned: thread tid < NXK its variable of the own record, the last knot's threads JP_V_STRIDE .. the six globals,
+// every thread its one or two owned rows.  Every element of both outputs is written exactly once; nothing else is written.
+// =====================================================================================================================
+struct alignas(16) SaddleDiagTables {
+    int32_t diag[JP_WG];   // variable i of a knot record: the block position of its diagonal entry in the Hessian run, -1: none (and behind NXK)
+};
+struct SaddleDiagArgs {
+    const JprodTables* jt;
+    const SaddleDiagTables* dt;
+    const double* hvals;    // [batch][nnz_h]
+    const double* jvals;    // [batch][nnz]
+    const double* dx;       // [batch][n] or null
+    const double* dc;       // [batch][m] or null
+    double* minv_top;       // [batch][n]
+    double* minv_bottom;    // [batch][m]
+    double floor;
+    int32_t N, n, m, nnz_first, nnz_interior, nnz_last, nnz_glob, nnz_knot;
+    int64_t nnz, glob_base, nnz_h;
+};
+constexpr int SD_MS = 0, SD_JS = SD_MS + JP_V_WORDS, SD_TW = SD_JS + JP_VALUES, SD_WORDS = SD_TW + JP_ENT_CAP / 2;
+static_assert(3 * ((SD_WORDS * int(sizeof(double)) + 1279) / 1280) * 1280 <= 160 * 1024, "three workgroups per CU");
+__global__ __launch_bounds__(JP_WG)
+void hipnlp_saddle_diag_kernel(SaddleDiagArgs a) {
+    constexpr int WG = JP_WG, JB = JP_BLOCK_CAP / WG, RQ = JP_ROW_CAP / WG;
+    static_assert(JP_BLOCK_CAP % WG == 0 && JP_OTHER_CAP <= WG && JP_GLOB_CAP <= WG && JP_V_STRIDE <= WG && JP_V_STRIDE + (JP_V_WORDS - JP_V_GLOB) <= WG && WG == 256, "staging by 256 threads");
+    __shared__ alignas(16) double lds[SD_WORDS];
+    double* ms = lds + SD_MS;
+    double* js = lds + SD_JS;
+    int32_t* tw = reinterpret_cast<int32_t*>(lds + SD_TW);
+    const int tid = threadIdx.x;
+    const int b = blockIdx.y, k = blockIdx.x, N = a.N;
+    const int first = k == 0, last = k == N - 1;
+    const int pv = first ? PV_FIRST : (last ? PV_LAST : (k == 1 ? PV_SECOND : PV_INTERIOR));
+    const JprodTables& jt = *a.jt;
+    const double* jvals = a.jvals + int64_t(b) * a.nnz;
+    const double* hvals = a.hvals + int64_t(b) * a.nnz_h;
+    const bool with_dx = a.dx != nullptr, with_dc = a.dc != nullptr;
+    const double* dxb = with_dx ? a.dx + int64_t(b) * a.n : nullptr;
+    auto block_len = [&](int kk) __attribute__((always_inline)) { return kk == 0 ? a.nnz_first : (kk == N - 1 ? a.nnz_last : a.nnz_interior); };
+    auto block_base = [&](int kk) __attribute__((always_inline)) { return kk == 0 ? int64_t(0) : int64_t(a.nnz_first) + int64_t(kk - 1) * a.nnz_interior; };
+    const bool col_thread = tid < NXK, glob_thread = tid >= JP_V_STRIDE && tid < JP_V_STRIDE + NXG;
+    // ---- the table words
+    int32_t ra[RQ], rb[RQ], dir[RQ];
+#pragma unroll
+    for (int it = 0; it < RQ; ++it) { const int q = tid + it * WG; ra[it] = jt.row_a[pv][q]; rb[it] = jt.row_b[pv][q]; dir[it] = jt.rdir[pv][q]; }
+    const int32_t dp = a.dt->diag[tid];
+    const bool has_diag = col_thread && dp >= 0 && dp < a.nnz_knot;
+    // ---- the jac run: own block, predecessor's block, the extras (phase 1 of the operator)
+    const int n_own = block_len(k), n_pred = first ? 0 : block_len(k - 1);
+    const double* own = jvals + block_base(k);
+    const double* pred = jvals + block_base(first ? 0 : k - 1);
+    double o[JB], p[JB];
+#pragma unroll
+    for (int it = 0; it < JB; ++it) { const int i = tid + it * WG; o[it] = i < n_own ? own[i] : 0.0; }
+#pragma unroll
+    for (int it = 0; it < JB; ++it) { const int i = tid + it * WG; p[it] = i < n_pred ? pred[i] : 0.0; }
+    double ex = 0.0;   // the entries of knot 0's block a last knot needs (threads 0 ..), the horizon-global run at knot 0 (threads 128 ..)
+    if (tid < JP_OTHER_CAP) {
+        const int32_t q = jt.other[tid];
+        if (last && q >= 0 && q < a.nnz_first) ex = jvals[q];
+    } else if (tid - JP_OTHER_CAP < JP_GLOB_CAP) {
+        const int i = tid - JP_OTHER_CAP;
+        if (first && i < a.nnz_glob) ex = jvals[a.glob_base + i];
+    }
+    // ---- the diagonal entries and d_x of the records: own knot, predecessor, other horizon end; the globals have no entry
+    double h0 = 0.0, h1 = 0.0, h2 = 0.0, x0 = 0.0, x1 = 0.0, x2 = 0.0;
+    if (col_thread) {
+        if (has_diag) {
+            h0 = hvals[int64_t(a.nnz_knot) * k + dp];
+            if (!first) h1 = hvals[int64_t(a.nnz_knot) * (k - 1) + dp];
+            if (last) h2 = hvals[dp];
+        }
+        if (with_dx) {
+            x0 = dxb[int64_t(NXK) * k + tid];
+            if (!first) x1 = dxb[int64_t(NXK) * (k - 1) + tid];
+            if (last) x2 = dxb[tid];
+        }
+    } else if (glob_thread && with_dx) {
+        x0 = dxb[int64_t(NXK) * N + (tid - JP_V_STRIDE)];
+    }
+    // ---- the entry words of the rows, d_c of the owned rows
+    int32_t wr[JP_WORDS_PER_THREAD];
+#pragma unroll
+    for (int it = 0; it < JP_WORDS_PER_THREAD; ++it) wr[it] = jt.word[pv][tid + it * WG];
+    double dcq[RQ];
+#pragma unroll
+    for (int it = 0; it < RQ; ++it) dcq[it] = (ra[it] != G_NONE && with_dc) ? a.dc[int64_t(b) * a.m + ra[it] + rb[it] * k] : 0.0;
+    // ---- minv_top of the records (zeros where the operator stages zeros of v), everything -> LDS
+    double m0 = 0.0, m1 = 0.0, m2 = 0.0;
+    if (col_thread) {
+        m0 = precond_top(with_dx, h0, x0, a.floor);
+        if (!first) m1 = precond_top(with_dx, h1, x1, a.floor);
+        if (last) m2 = precond_top(with_dx, h2, x2, a.floor);
+    } else if (glob_thread) {
+        m0 = precond_top(with_dx, 0.0, x0, a.floor);
+    }
+    if (tid < JP_V_STRIDE) { ms[tid] = m0; ms[JP_V_PRED + tid] = m1; ms[JP_V_OTHER + tid] = m2; }
+    else if (tid - JP_V_STRIDE < JP_V_WORDS - JP_V_GLOB) ms[JP_V_GLOB + (tid - JP_V_STRIDE)] = m0;
+#pragma unroll
+    for (int it = 0; it < JB; ++it) { js[tid + it * WG] = o[it]; js[JP_POS_PRED + tid + it * WG] = p[it]; }
+#pragma unroll
+    for (int it = 0; it < JP_WORDS_PER_THREAD; ++it) tw[tid + it * WG] = wr[it];
+    if (tid < JP_OTHER_CAP + JP_GLOB_CAP) js[JP_POS_OTHER + tid] = ex;   // (JP_POS_GLOB == JP_POS_OTHER + JP_OTHER_CAP)
+    __syncthreads();
+    // ---- the owned rows, and both outputs
+    {
+        double* out = a.minv_bottom + int64_t(b) * a.m;
+#pragma unroll
+        for (int it = 0; it < RQ; ++it)
+            if (ra[it] != G_NONE) out[ra[it] + rb[it] * k] = precond_bottom(with_dc, dcq[it], precond_row_staged(dir[it], tw, js, ms), a.floor);
+    }
+    if (col_thread) a.minv_top[int64_t(b) * a.n + int64_t(NXK) * k + tid] = m0;
+    else if (last && glob_thread) a.minv_top[int64_t(b) * a.n + int64_t(NXK) * N + (tid - JP_V_STRIDE)] = m0;
+}
+
+
 // Throughput variant only (4 waves; the latency variant sums inside the knot kernel, see pub_step): f[b] = sum over knots and
 // terms, cost_terms[b][t] = sum over knots.  One workgroup per trajectory.  Thread (group g = tid / 16, column c = tid % 16) sums
 // column c of the knots g, g + 16, ...: all its loads are independent and issued together (ONE memory round trip), then a fixed
@@ -2134,6 +2265,7 @@ struct hipnlp_handle {
     double* d_jdot = nullptr;
     double* d_minres = nullptr;          // the workspace of hipnlp_kkt_minres_device: vectors, partials, scalar records (one allocation)
     int32_t* h_minres_status = nullptr;  // pinned [batch]: the statuses a check_every > 0 solve looks at
+    SaddleDiagTables* d_dt = nullptr;    // hipnlp_kkt_diag_precond_device: the diagonal positions of the Hessian block, uploaded at the first call
     std::string err;
 };
 
@@ -2188,7 +2320,7 @@ static void free_all(hipnlp_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->dev);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* dptrs[] = {h->d_tb, h->d_ctpl, h->d_ctpl_of_b, h->d_healed, h->d_x, h->d_pk, h->d_cost_knot, h->d_gp, h->d_cost_pub, h->d_out, h->d_ht, h->d_sigma, h->d_hess, h->d_hflag, h->d_htrash, h->d_lt, h->d_vt, h->d_jt, h->d_jtt, h->d_jdot, h->d_minres};
+    void* dptrs[] = {h->d_tb, h->d_ctpl, h->d_ctpl_of_b, h->d_healed, h->d_x, h->d_pk, h->d_cost_knot, h->d_gp, h->d_cost_pub, h->d_out, h->d_ht, h->d_sigma, h->d_hess, h->d_hflag, h->d_htrash, h->d_lt, h->d_vt, h->d_jt, h->d_jtt, h->d_jdot, h->d_minres, h->d_dt};
     for (void* q : dptrs) if (q) (void)hipFree(q);
     void* hptrs[] = {h->h_x, h->h_out, h->h_hess, h->h_hflag, h->h_sl, h->h_minres_status};
     for (void* q : hptrs) if (q) (void)hipHostFree(q);
@@ -3643,6 +3775,36 @@ int hipnlp_kkt_minres_device(hipnlp_handle* h, const double* hess_values_dev, co
             if (!running) break;
         }
     }
+    return HIPNLP_OK;
+}
+// ---- the diagonal preconditioner of that solve (include/hipnlp.h; knot_kkt_precond.h) -------------------------------------------------------
+int hipnlp_kkt_diag_precond_device(hipnlp_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev, const double* dc_dev, double floor,
+                                   double* minv_top_dev, double* minv_bottom_dev, void* stream) {
+    if (!h || !hess_values_dev || !jac_values_dev || !minv_top_dev || !minv_bottom_dev) return HIPNLP_E_INVALID;
+    if (!(floor > 0.0) || !minres_finite(floor)) { h->err = "hipnlp_kkt_diag_precond_device: floor must be a finite number > 0"; return HIPNLP_E_INVALID; }
+    NOT_FRONT(h, "hipnlp_kkt_diag_precond_device");
+    if (const int rc = whole_horizon_only(h, "hipnlp_kkt_diag_precond_device", "a row of g has entries in the blocks of two knots, the periodicity rows need both horizon ends")) return rc;
+    if (const int rc = jprod_prepare(h, "hipnlp_kkt_diag_precond_device")) return rc;
+    if (const int rc = hvp_prepare(h, "hipnlp_kkt_diag_precond_device")) return rc;   // (the Hessian layout, and that its entries stay inside a knot record)
+    const Layout& L = h->L;
+    const HessLayout& HL = h->HL;
+    if (!h->d_dt) {
+        SaddleDiagTables* t = new SaddleDiagTables();
+        for (int i = 0; i < JP_WG; ++i) t->diag[i] = i < NXK ? HL.hv_diag[size_t(i)] : -1;
+        const int rc = upload_table(h, reinterpret_cast<void**>(&h->d_dt), t, sizeof(SaddleDiagTables), "Hessian diagonal positions");
+        delete t;
+        if (rc != HIPNLP_OK) return rc;
+    }
+    HIP_TRY(h, hipSetDevice(h->dev));
+    SaddleDiagArgs a;
+    a.jt = h->d_jt; a.dt = h->d_dt; a.hvals = hess_values_dev; a.jvals = jac_values_dev; a.dx = dx_dev; a.dc = dc_dev;
+    a.minv_top = minv_top_dev; a.minv_bottom = minv_bottom_dev; a.floor = floor;
+    a.N = L.N; a.n = L.n; a.m = L.m;
+    a.nnz_first = L.nnz_v[VAR_FIRST]; a.nnz_interior = L.nnz_v[VAR_INTERIOR]; a.nnz_last = L.nnz_v[VAR_LAST]; a.nnz_glob = int32_t(L.jperm_glob.size());
+    a.nnz_knot = HL.nnz_knot;
+    a.nnz = L.nnz; a.glob_base = L.jac_glob_base; a.nnz_h = hess_count(h);
+    hipLaunchKernelGGL(hipnlp_saddle_diag_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(JP_WG), 0, stream ? hipStream_t(stream) : h->stream, a);
+    HIP_TRY(h, hipGetLastError());
     return HIPNLP_OK;
 }
 // how a handle in auto mode (hipnlp_set_hessian_early_run(h, -1)) came to its choice

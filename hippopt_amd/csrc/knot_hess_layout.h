@@ -34,6 +34,9 @@ struct HessLayout {
     // (else hvp_error).
     std::vector<HvpTouch> hv_touch;
     std::vector<int32_t> hv_beg, hv_K, hv_couple;
+    // hv_diag[i]: the block position of the DIAGONAL entry of variable i of a knot record — its touch whose other variable is i itself —
+    // or -1 where the pattern has none (the diagonal preconditioner of knot_kkt_precond.h gathers it)
+    std::vector<int32_t> hv_diag;
     bool hvp_ok = false;
     std::string hvp_error;
     std::string error;
@@ -111,9 +114,12 @@ struct HessLayout {
         hv_beg.assign(NXK + 1, 0);
         hv_K.assign(NXK, 0);
         hv_couple.assign(NXK, -1);
+        hv_diag.assign(NXK, -1);
         if (!hvp_ok) return;
         for (int i = 0; i < NXK; ++i) {
             hv_K[size_t(i)] = int32_t(per[size_t(i)].size());
+            for (const HvpTouch& t : per[size_t(i)])
+                if (t.other == i) hv_diag[size_t(i)] = t.pos;   // (at most one: duplicate entries are refused above)
             hv_touch.insert(hv_touch.end(), per[size_t(i)].begin(), per[size_t(i)].end());
             hv_beg[size_t(i) + 1] = int32_t(hv_touch.size());
         }

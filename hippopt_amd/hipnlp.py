@@ -29,6 +29,7 @@ EXPORTS = [
     "hipnlp_hess_nnz", "hipnlp_hess_sparsity", "hipnlp_eval_hess", "hipnlp_eval_hess_at", "hipnlp_set_hessian_early_run", "hipnlp_get_hessian_early_run", "hipnlp_hessian_early_run_reason", "hipnlp_eval_hess_device",
     "hipnlp_eval_lagrangian_grad_device", "hipnlp_eval_hess_vec_device", "hipnlp_hess_times_device",
     "hipnlp_jac_times_device", "hipnlp_jac_transpose_times_device", "hipnlp_kkt_times_device", "hipnlp_kkt_minres_device", "hipnlp_kkt_minres_reserve",
+    "hipnlp_kkt_diag_precond_device",
     "hipnlp_eval_pinned", "hipnlp_set_prefetch", "hipnlp_set_early_outputs", "hipnlp_set_host_timing", "hipnlp_host_register", "hipnlp_host_unregister",
     "hipnlp_multi_create", "hipnlp_multi_plan", "hipnlp_multi_info", "hipnlp_multi_breakdown", "hipnlp_multi_set_threads",
     "hipnlp_host_breakdown", "hipnlp_set_auto_register", "hipnlp_host_stats", "hipnlp_set_constant_jacobian", "hipnlp_forget_jac_destination", "hipnlp_jac_constant_mask", "hipnlp_host_release_auto_ranges",
@@ -225,6 +226,8 @@ def load_library(path=None):
     if hasattr(lib, "hipnlp_kkt_minres_device"):
         lib.hipnlp_kkt_minres_device.argtypes = [vp] * 11 + [C.c_double, C.c_int, C.c_int] + [vp] * 4
         lib.hipnlp_kkt_minres_reserve.argtypes = [vp, C.POINTER(C.c_int64)]
+    if hasattr(lib, "hipnlp_kkt_diag_precond_device"):
+        lib.hipnlp_kkt_diag_precond_device.argtypes = [vp] * 5 + [C.c_double] + [vp] * 3
     _libs[path] = lib
     return lib
 
@@ -641,6 +644,15 @@ class HipNlp:
                                                       vp(minv_top_ptr or None), vp(minv_bottom_ptr or None), vp(rhs_top_ptr or None), vp(rhs_bottom_ptr or None),
                                                       vp(sol_top_ptr or None), vp(sol_bottom_ptr or None), float(rtol), int(max_iterations), int(check_every),
                                                       vp(iterations_ptr or None), vp(residual_ptr or None), vp(status_ptr or None), vp(stream or None)))
+
+    def kkt_diag_precond_device(self, hess_values_ptr, jac_values_ptr, minv_top_ptr, minv_bottom_ptr, dx_ptr=0, dc_ptr=0, floor=1e-10, stream=0):
+        """The diagonal preconditioner of kkt_minres_device in ONE launch (hipnlp_kkt_diag_precond_device), from the value runs and
+        diagonals of kkt_times_device: minv_top [batch][n] = 1 / max(|H_jj + dx_j|, floor) and minv_bottom [batch][m] =
+        1 / max(|dc_i + sum_e J_ie^2 minv_top_col(e)|, floor); dx / dc are optional (0: that term is left out); floor > 0 (the default is
+        untuned); a NaN or an infinity of the inputs comes out as NaN; asynchronous on `stream`; the outputs may not alias the inputs"""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_kkt_diag_precond_device(self.h, vp(hess_values_ptr or None), vp(jac_values_ptr or None), vp(dx_ptr or None), vp(dc_ptr or None),
+                                                            float(floor), vp(minv_top_ptr or None), vp(minv_bottom_ptr or None), vp(stream or None)))
 
     def kkt_minres_reserve(self):
         """allocate the handle's MINRES workspace now (otherwise: on the first solve); returns its size in bytes"""

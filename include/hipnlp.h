@@ -512,7 +512,7 @@ int hipnlp_kkt_times_device(hipnlp_handle* h, const double* hess_values_dev, con
  *
  * from the two value runs and the diagonals of hipnlp_kkt_times_device (same rules).  The start is zero (a caller who wants a warm start
  * solves for the correction).  The preconditioner M^-1 = diag(minv_top_dev [batch][n], minv_bottom_dev [batch][m]) > 0 is the caller's;
- * both NULL: the identity, nothing is read.  Building a preconditioner is not part of the library.  rhs_top_dev, sol_top_dev [batch][n];
+ * both NULL: the identity, nothing is read.  hipnlp_kkt_diag_precond_device (below) builds a diagonal one.  rhs_top_dev, sol_top_dev [batch][n];
  * rhs_bottom_dev, sol_bottom_dev [batch][m]; iterations_dev, status_dev (int32) and residual_dev [batch].  residual is phibar / beta1:
  * the relative residual in the M^-1 norm, sqrt(r . M^-1 r) / sqrt(b . M^-1 b), as the recurrence estimates it.
  *
@@ -542,7 +542,8 @@ int hipnlp_kkt_times_device(hipnlp_handle* h, const double* hess_values_dev, con
  * caller's events).  The outputs may not alias the inputs; nothing but the six outputs and the workspace is written.
  *
  * NOT claimed: convergence on the KKT systems of real iterates — they are indefinite and badly scaled (entries reach 1e8 on the stairs
- * terrain) and no preconditioner is built here; the tests converge on conditioned synthetic value runs only.
+ * terrain).  The tests converge on conditioned synthetic value runs, and on symmetrically rescaled ones (cond up to 1e16) with the diagonal
+ * of hipnlp_kkt_diag_precond_device; what that diagonal did on real value runs is recorded there.
  *
  * Returns as hipnlp_kkt_times_device (HIPNLP_E_INVALID for a missing handle or required pointer — all but dx_dev, dc_dev and the two
  * minv; HIPNLP_E_UNSUPPORTED on a multi-device handle, a shard handle, a layout beyond the caps), and HIPNLP_E_INVALID for rtol < 0,
@@ -552,6 +553,39 @@ int hipnlp_kkt_minres_device(hipnlp_handle* h, const double* hess_values_dev, co
                              const double* rhs_bottom_dev, double* sol_top_dev, double* sol_bottom_dev, double rtol, int max_iterations,
                              int check_every, int32_t* iterations_dev, double* residual_dev, int32_t* status_dev, void* stream);
 int hipnlp_kkt_minres_reserve(hipnlp_handle* h, int64_t* bytes_out);
+
+/* The diagonal preconditioner of that solve, built on the device from the same two value runs and diagonals, in ONE launch on the
+ * operator's grid (knots, batch):
+ *
+ *     minv_top_dev    [batch][n]:  1 / max(|H_jj + d_x,j|, floor)      H_jj: the stored diagonal entry of variable j, +0.0 where the pattern
+ *                                                                      has none (the six horizon-global variables)
+ *     minv_bottom_dev [batch][m]:  1 / max(|d_c,i + sum_e J_ie^2 minv_top_col(e)|, floor)
+ *
+ * ready to be passed to hipnlp_kkt_minres_device.  The absolute value on the top is deliberate: H + diag d_x is indefinite at real
+ * iterates and MINRES needs M positive definite.  dx_dev / dc_dev may be NULL (that term is left out, nothing is read); floor > 0 keeps
+ * the reciprocals finite.  A NaN or an infinity in the inputs is not clamped away: every output that depends on it is NaN, and the solve
+ * ends that trajectory with status 2.  Pointer, stream and aliasing rules of hipnlp_kkt_times_device.
+ *
+ * Order of every sum (knot_kkt_precond.h has the rounding sequence): the divisions are correctly rounded; a row's sum is ONE chain from
+ * +0.0 over its entries in the order of hipnlp_jac_times_device (ascending global column), per entry q = J_ie * J_ie rounded, then one
+ * fused multiply-add with minv_top of the column; d_c,i is added last.  No workgroup waits for another and there are no atomics: the
+ * workgroup of a row's owner knot recomputes minv_top of the columns it needs (its own knot's, its predecessor's, the other horizon
+ * end's, the globals') from one Hessian value and one d_x each.  So the same bits at every position of a batch and for both jac orders.
+ * Every element of minv_top_dev and minv_bottom_dev is written exactly once, by the workgroup that writes that element of
+ * hipnlp_kkt_times_device's outputs; nothing else is written.  No workspace.
+ *
+ * What is claimed: on symmetrically rescaled systems K' = S K S the preconditioned iteration count is, up to rounding, that of the
+ * unscaled system (the tests: status 0 after 23 to 25 iterations at cond(K') about 1e12, where the identity ends at status 1 after 300).  On
+ * the real N = 4 value runs of the tests (d_x, d_c in U[1, 2]: not an interior-point method's) the diagonal was the difference between
+ * status 0 (after about 2 200 iterations) and status 1 at 3 000 on the stairs terrain, and about a fifth fewer iterations on the planar one.
+ * NOT claimed: that an interior-point step is cheap with it, or anything about larger systems beyond what profiles/r13_kkt_precond.txt
+ * records (at 100 and 200 knots no trajectory converged within 3 000 iterations, with or without it).
+ *
+ * Returns as hipnlp_kkt_times_device (HIPNLP_E_INVALID for a missing handle or required pointer — all but dx_dev and dc_dev;
+ * HIPNLP_E_UNSUPPORTED on a multi-device handle, a shard handle, a layout beyond the caps), and HIPNLP_E_INVALID for a floor that is not
+ * a finite number > 0. */
+int hipnlp_kkt_diag_precond_device(hipnlp_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev,
+                                   const double* dc_dev, double floor, double* minv_top_dev, double* minv_bottom_dev, void* stream);
 
 /* Sharded variant (multi-GPU): the handle owns knots [knot_begin, knot_end).  Outputs are
  * shard-local and contiguous so that one RCCL all-gather reassembles them:
