@@ -39,6 +39,7 @@
 #include "knot_kkt_precond.h"
 #include "knot_minres.h"
 #include "knot_stage.h"
+#include "knot_values_stage.h"
 #include "layout.h"
 
 using namespace hipnlp;
@@ -1095,47 +1096,28 @@ struct TArgs {
     const double* values;   // [batch][nnz_h]
     const double* v;        // [batch][n]
     double* out;            // [batch][n]
-    int32_t N, n, nnz_knot, n_couple;
-    int64_t nnz_h;
+    int32_t N, n;
+    HessRunDims hd;
 };
 __global__ __launch_bounds__(256)
 void hipnlp_hess_times_kernel(TArgs a) {
-    constexpr int WG = 256;
-    constexpr int HB = (hk::COUNT + WG - 1) / WG;
-    __shared__ double hv[HB * WG];
+    using Stage = HessBlockStage<HvpTables>;
+    __shared__ double hv[Stage::HB * Stage::WG];
     __shared__ int32_t tw[HVP_WORD_CAP];
     __shared__ double vs[XPAD];
+    const HessRunDims& hd = a.hd;
     const int tid = threadIdx.x;
     const int b = blockIdx.y, k = blockIdx.x, N = a.N;
-    const int first = k == 0, last = k == N - 1;
-    const HvpTables& vt = *a.vt;
-    const double* vals = a.values + int64_t(b) * a.nnz_h;
-    const double* blk = vals + int64_t(a.nnz_knot) * k;
+    const int last = k == N - 1;
     const double* vb = a.v + size_t(b) * a.n;
-    double h[HB];
-    int32_t wr[HVP_WORDS_PER_THREAD];
-#pragma unroll
-    for (int it = 0; it < HB; ++it) { const int i = tid + it * WG; h[it] = i < a.nnz_knot ? blk[i] : 0.0; }
-#pragma unroll
-    for (int it = 0; it < HVP_WORDS_PER_THREAD; ++it) wr[it] = vt.word_pos[tid + it * WG];
-    const int32_t row = vt.row[tid];
-    double vk = 0.0, vo = 0.0, cpl = 0.0;
-    if (tid < NXK) {
-        vk = vb[size_t(NXK) * k + tid];
-        if (a.n_couple > 0 && (first || last) && ((row >> HVP_COUPLED_BIT) & 1)) {
-            vo = vb[size_t(NXK) * (first ? N - 1 : 0) + tid];
-            cpl = vals[int64_t(a.nnz_knot) * N + vt.couple[tid]];
-        }
-    }
-#pragma unroll
-    for (int it = 0; it < HB; ++it) hv[tid + it * WG] = h[it];
-#pragma unroll
-    for (int it = 0; it < HVP_WORDS_PER_THREAD; ++it) tw[tid + it * WG] = wr[it];
+    Stage hs(tid);
+    hs.issue(*a.vt, hd, a.values + int64_t(b) * hd.nnz_h, vb, k, N);
+    const double vk = tid < NXK ? vb[size_t(NXK) * k + tid] : 0.0;
+    hs.land(hv, tw);
     if (tid < XPAD) vs[tid] = vk;
     __syncthreads();
     if (tid < NXK) {
-        const bool on = a.n_couple > 0 && (first || last);
-        const double y = hvp_thread_row(on ? row : row & ~(1 << HVP_COUPLED_BIT), tw, vs, [&](int pos) __attribute__((always_inline)) { return hv[pos]; }, cpl, vo);
+        const double y = hvp_thread_row(hs.row_word(), tw, vs, [&](int pos) __attribute__((always_inline)) { return hv[pos]; }, hs.cpl, hs.vo);
         a.out[int64_t(b) * a.n + int64_t(NXK) * k + tid] = y;
     } else if (last && tid >= HVP_SPAN_GLOB && tid < HVP_SPAN_GLOB + NXG) {
         a.out[int64_t(b) * a.n + int64_t(NXK) * N + (tid - HVP_SPAN_GLOB)] = 0.0;
@@ -1284,8 +1266,7 @@ struct JArgs {
     const double* v;        // [batch][n]
     double* jv;             // [batch][m] or null
     double* dot_part;       // [batch][N] or null (needs grad)
-    int32_t N, n, m, nnz_first, nnz_interior, nnz_last, nnz_glob;
-    int64_t nnz, glob_base;
+    JacRunDims jd;
 };
 __global__ __launch_bounds__(JP_WG)
 void hipnlp_jac_times_kernel(JArgs a) {
@@ -1294,58 +1275,21 @@ void hipnlp_jac_times_kernel(JArgs a) {
     __shared__ double vs[JP_V_WORDS];
     __shared__ int32_t tw[JP_ENT_CAP];
     __shared__ double part[WG / 64];
-    static_assert(JP_BLOCK_CAP % WG == 0 && JP_OTHER_CAP <= WG && JP_GLOB_CAP <= WG && JP_V_STRIDE <= WG && JP_ROW_CAP == 2 * WG, "jprod staging by 256 threads");
     static_assert(sizeof(double) * (JP_VALUES + JP_V_WORDS + WG / 64) + sizeof(int32_t) * JP_ENT_CAP <= 160 * 1024 / 3, "three workgroups per CU");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int b = blockIdx.y, k = blockIdx.x, N = a.N;
-    const int first = k == 0, last = k == N - 1;
-    const int pv = first ? PV_FIRST : (last ? PV_LAST : (k == 1 ? PV_SECOND : PV_INTERIOR));
+    const JacRunDims& jd = a.jd;
+    const int tid = threadIdx.x;
+    const int b = blockIdx.y, k = blockIdx.x, N = jd.N;
+    const int pv = pair_variant(k, N);
     const JprodTables& jt = *a.jt;
-    const double* vals = a.values + int64_t(b) * a.nnz;
-    const double* vb = a.v + int64_t(b) * a.n;
-    auto block_len = [&](int kk) __attribute__((always_inline)) { return kk == 0 ? a.nnz_first : (kk == N - 1 ? a.nnz_last : a.nnz_interior); };
-    auto block_base = [&](int kk) __attribute__((always_inline)) { return kk == 0 ? int64_t(0) : int64_t(a.nnz_first) + int64_t(kk - 1) * a.nnz_interior; };
-    const double gk = (a.dot_part && tid < NXK) ? a.grad[int64_t(b) * a.n + int64_t(NXK) * k + tid] : 0.0;
-    // the records of v: own knot, predecessor, other horizon end (last knot), the globals
-    if (tid < JP_V_STRIDE) {
-        const bool on = tid < NXK;
-        vs[tid] = on ? vb[int64_t(NXK) * k + tid] : 0.0;
-        vs[JP_V_PRED + tid] = (on && !first) ? vb[int64_t(NXK) * (k - 1) + tid] : 0.0;
-        vs[JP_V_OTHER + tid] = (on && last) ? vb[tid] : 0.0;
-    } else if (tid - JP_V_STRIDE < JP_V_WORDS - JP_V_GLOB) {
-        const int i = tid - JP_V_STRIDE;
-        vs[JP_V_GLOB + i] = i < NXG ? vb[int64_t(NXK) * N + i] : 0.0;
-    }
-    if (a.jv) {
-        constexpr int JB = JP_BLOCK_CAP / WG;
-        const int n_own = block_len(k), n_pred = first ? 0 : block_len(k - 1);
-        const double* own = vals + block_base(k);
-        const double* pred = vals + block_base(first ? 0 : k - 1);
-        double o[JB], p[JB];
-        int32_t wr[JP_WORDS_PER_THREAD];
-#pragma unroll
-        for (int it = 0; it < JB; ++it) { const int i = tid + it * WG; o[it] = i < n_own ? own[i] : 0.0; }
-#pragma unroll
-        for (int it = 0; it < JB; ++it) { const int i = tid + it * WG; p[it] = i < n_pred ? pred[i] : 0.0; }
-#pragma unroll
-        for (int it = 0; it < JP_WORDS_PER_THREAD; ++it) wr[it] = jt.word[pv][tid + it * WG];
-        double ex = 0.0;   // the entries of knot 0's block a last knot needs (threads 0 ..), the horizon-global run at knot 0 (threads 128 ..)
-        if (tid < JP_OTHER_CAP) {
-            const int32_t q = jt.other[tid];
-            if (last && q >= 0 && q < a.nnz_first) ex = vals[q];
-        } else if (tid - JP_OTHER_CAP < JP_GLOB_CAP) {
-            const int i = tid - JP_OTHER_CAP;
-            if (first && i < a.nnz_glob) ex = vals[a.glob_base + i];
-        }
-#pragma unroll
-        for (int it = 0; it < JB; ++it) { js[tid + it * WG] = o[it]; js[JP_POS_PRED + tid + it * WG] = p[it]; }
-#pragma unroll
-        for (int it = 0; it < JP_WORDS_PER_THREAD; ++it) tw[tid + it * WG] = wr[it];
-        if (tid < JP_OTHER_CAP + JP_GLOB_CAP) js[JP_POS_OTHER + tid] = ex;   // (JP_POS_GLOB == JP_POS_OTHER + JP_OTHER_CAP)
-    }
+    const double gk = (a.dot_part && tid < NXK) ? a.grad[int64_t(b) * jd.n + int64_t(NXK) * k + tid] : 0.0;
+    RecordStage rec(tid); JacRowStage rows(tid);
+    rec.issue(a.v + int64_t(b) * jd.n, k, N);
+    if (a.jv) rows.issue(jt, jd, a.values + int64_t(b) * jd.nnz, k);
+    rec.land(vs, rec.r0, rec.r1, rec.r2);
+    if (a.jv) rows.land(js, tw);
     __syncthreads();
     if (a.jv) {
-        double* out = a.jv + int64_t(b) * a.m;
+        double* out = a.jv + int64_t(b) * jd.m;
 #pragma unroll
         for (int it = 0; it < JP_ROW_CAP / WG; ++it) {
             const int q = tid + it * WG;
@@ -1354,16 +1298,11 @@ void hipnlp_jac_times_kernel(JArgs a) {
         }
     }
     if (a.dot_part) {
-        // grad f . v of this knot: one product per thread, a butterfly over the lanes, then the waves in order (knot_jprod.h jprod_dot_tree)
-        double acc = tid < NXK ? jprod_dot_product(gk, vs[tid]) : 0.0;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) acc += __shfl_xor(acc, s, 64);
-        if (lane == 0) part[wave] = acc;
-        __syncthreads();
-        if (tid == 0) a.dot_part[int64_t(b) * N + k] = ((part[0] + part[1]) + part[2]) + part[3];
+        // grad f . v of this knot: one product per thread, then the tree (knot_jprod.h jprod_dot_tree)
+        const double sum = workgroup_tree(tid < NXK ? jprod_dot_product(gk, vs[tid]) : 0.0, part);
+        if (tid == 0) a.dot_part[int64_t(b) * N + k] = sum;
     }
 }
-static_assert(JP_POS_GLOB == JP_POS_OTHER + JP_OTHER_CAP && JP_WG / 64 == 4, "hipnlp_jac_times_kernel: the extra runs are staged side by side; four waves");
 // dot[b] = the per-knot partials of trajectory b in ascending knot order, from +0.0: one thread per trajectory
 __global__ __launch_bounds__(64) void hipnlp_jac_dot_reduce_kernel(const double* part, int N, int batch, double* dot) {
     const int b = blockIdx.x * 64 + threadIdx.x;
@@ -1381,51 +1320,42 @@ struct JTArgs {
     const double* sigma;    // [batch] or null with grad null
     const double* lambda;   // [batch][m]
     double* out;            // [batch][n]
-    int32_t N, n, m, nnz_first, nnz_interior, nnz_last, nnz_glob;
-    int64_t nnz, glob_base;
+    JacRunDims jd;
 };
 __global__ __launch_bounds__(256)
 void hipnlp_jac_transpose_times_kernel(JTArgs a) {
-    constexpr int WG = 256, JB = LG_ENT_CAP / WG, LQ = LG_LAM_CAP / WG;
+    using Stage = JacColumnStage<LgradTables>;
+    constexpr int WG = Stage::WG, JB = Stage::JB;
     __shared__ double js[LG_ENT_CAP + 16];
     __shared__ double ls[LG_LAM_CAP];
     __shared__ int32_t lw[LG_ENT_CAP + 16];
+    const JacRunDims& jd = a.jd;
     const int tid = threadIdx.x;
-    const int b = blockIdx.y, k = blockIdx.x, N = a.N;
-    const int first = k == 0, last = k == N - 1;
-    const int v = first ? VAR_FIRST : (last ? VAR_LAST : VAR_INTERIOR);
+    const int b = blockIdx.y, k = blockIdx.x, N = jd.N;
+    const int last = k == N - 1;
+    const int v = block_variant(k, N);
     const LgradTables& lt = *a.tt;
-    const double* vals = a.values + int64_t(b) * a.nnz;
-    const double* own = vals + (first ? int64_t(0) : int64_t(a.nnz_first) + int64_t(k - 1) * a.nnz_interior);
-    const double* lam = a.lambda + int64_t(b) * a.m;
-    const int n_own = first ? a.nnz_first : (last ? a.nnz_last : a.nnz_interior);
-    double o[JB], lv[LQ];
-    int32_t w[JB];
+    const double* vals = a.values + int64_t(b) * jd.nnz;
+    const double* own = vals + jd.block_base(k);
+    const int n_own = jd.block_len(k);
+    Stage cols(tid);
+    cols.issue_rows(lt, v);
+    double o[JB];   // the own block's values: this kernel's alone (the operator has them from its row stage)
 #pragma unroll
     for (int it = 0; it < JB; ++it) { const int i = tid + it * WG; o[it] = i < n_own ? own[i] : 0.0; }
-#pragma unroll
-    for (int it = 0; it < LQ; ++it) {
-        const int32_t ra = lt.row_a[v][tid + it * WG], rb = lt.row_b[v][tid + it * WG];
-        lv[it] = ra != G_NONE ? lam[ra + rb * k] : 0.0;
-    }
-#pragma unroll
-    for (int it = 0; it < JB; ++it) w[it] = lt.word[v][tid + it * WG];
-    const int32_t wg = lt.word[v][LG_ENT_CAP + (tid & 15)];
-    const int32_t e0 = lt.beg[v][tid], e1 = lt.end[v][tid];
-    const double og = (last && tid < 16 && tid < a.nnz_glob) ? vals[a.glob_base + tid] : 0.0;
+    cols.issue_multipliers(a.lambda + int64_t(b) * jd.m, k);
+    cols.issue(lt, v, jd, vals, k);
     const bool with_grad = a.grad != nullptr;
     const double sig = with_grad ? a.sigma[b] : 0.0;
-    const double gc = (with_grad && tid < NXK) ? a.grad[int64_t(b) * a.n + int64_t(NXK) * k + tid] : 0.0;
+    const double gc = (with_grad && tid < NXK) ? a.grad[int64_t(b) * jd.n + int64_t(NXK) * k + tid] : 0.0;
 #pragma unroll
-    for (int it = 0; it < JB; ++it) { js[tid + it * WG] = o[it]; lw[tid + it * WG] = w[it]; }
-#pragma unroll
-    for (int it = 0; it < LQ; ++it) ls[tid + it * WG] = lv[it];
-    if (tid < 16) { js[LG_ENT_CAP + tid] = og; lw[LG_ENT_CAP + tid] = wg; }
+    for (int it = 0; it < JB; ++it) js[tid + it * WG] = o[it];
+    cols.land(lw, ls, js + LG_ENT_CAP);
     __syncthreads();
     if (tid < NXK) {
-        a.out[int64_t(b) * a.n + int64_t(NXK) * k + tid] = jprod_column_staged(with_grad, sig, gc, e0, e1, lw, ls, js);
+        a.out[int64_t(b) * jd.n + int64_t(NXK) * k + tid] = jprod_column_staged(with_grad, sig, gc, cols.e0, cols.e1, lw, ls, js);
     } else if (last && tid >= LG_SPAN_GLOB && tid < LG_SPAN_GLOB + NXG) {   // the global variables carry no cost
-        a.out[int64_t(b) * a.n + int64_t(NXK) * N + (tid - LG_SPAN_GLOB)] = jprod_column_staged(with_grad, sig, 0.0, e0, e1, lw, ls, js);
+        a.out[int64_t(b) * jd.n + int64_t(NXK) * N + (tid - LG_SPAN_GLOB)] = jprod_column_staged(with_grad, sig, 0.0, cols.e0, cols.e1, lw, ls, js);
     }
 }
 
@@ -1438,9 +1368,9 @@ void hipnlp_jac_transpose_times_kernel(JTArgs a) {
 // the columns of jac g are knot-local, every row of g has one owner knot.  No knot program, no x, no parameters, no non-finite flag, no
 // atomics, no exchange between workgroups.
 //   loads: everything is requested before the first LDS write (one memory round trip; only the multipliers of the owned rows and of the
-//   column sums wait for their table words first): the own and the predecessor's block of the jac run, the extras (the last knot's
-//   entries of knot 0's block, the horizon-global run at knot 0 — and at the last knot, for its six global columns), the records of v,
-//   the multipliers w of LgradTables::row_a / row_b, the knot's block of the Hessian run with the coupling value, the three word tables.
+//   column sums wait for their table words first), by the stages of knot_values_stage.h: JacRowStage and RecordStage (v) with
+//   hipnlp_jac_times_kernel, JacColumnStage (w, the global run at the last knot) with hipnlp_jac_transpose_times_kernel, HessBlockStage
+//   with hipnlp_hess_times_kernel — one text each.
 //   phase 1: the jac values, both entry-word tables, v and w go into LDS; after the barrier every thread finishes its column of J^T w
 //   (jprod_column_staged, as hipnlp_jac_transpose_times_kernel without a gradient) and its one or two owned rows of J v
 //   (jprod_row_staged, as hipnlp_jac_times_kernel) INTO REGISTERS, and stores its rows of bottom.
@@ -1463,12 +1393,12 @@ struct KktArgs {
     const double* w;        // [batch][m]
     double* top;            // [batch][n]
     double* bottom;         // [batch][m]
-    int32_t N, n, m, nnz_first, nnz_interior, nnz_last, nnz_glob, nnz_knot, n_couple;
-    int64_t nnz, glob_base, nnz_h;
+    JacRunDims jd;
+    HessRunDims hd;
 };
 // the LDS of a workgroup, in doubles: the records of v live through both phases; the Hessian block and its touch words lie over the jac
 // values and the row entry words
-constexpr int KK_HB = (hk::COUNT + JP_WG - 1) / JP_WG;
+constexpr int KK_HB = HessBlockStage<HvpTables>::HB;
 constexpr int KK_VS = 0, KK_JS = KK_VS + JP_V_WORDS, KK_TW = KK_JS + JP_VALUES, KK_LW = KK_TW + JP_ENT_CAP / 2, KK_LS = KK_LW + (LG_ENT_CAP + 16) / 2;
 constexpr int KK_JG = KK_LS + LG_LAM_CAP, KK_WORDS = KK_JG + 16;
 constexpr int KK_HV = KK_JS, KK_HW = KK_HV + KK_HB * JP_WG;
@@ -1477,15 +1407,6 @@ static_assert(KK_HW + HVP_WORD_CAP / 2 <= KK_WORDS && HVP_WORD_CAP % 2 == 0, "th
 static_assert(KK_JG >= LG_ENT_CAP && JP_GLOB_CAP <= 16, "the horizon-global run of the last knot is addressed from LG_ENT_CAP on");
 static_assert(2 * ((KK_WORDS * int(sizeof(double)) + 1279) / 1280) * 1280 <= 160 * 1024, "two workgroups per CU");
 static_assert(LG_SPAN_GLOB == JP_V_STRIDE && LG_SPAN_GLOB == HVP_SPAN_GLOB, "the threads of the global columns stage the global elements of v");
-// the tree of jprod_dot_tree over a workgroup's 256 per-thread values: a butterfly over the lanes, then the four waves in order (every
-// thread returns the sum; part: four doubles of LDS, one call per launch)
-__device__ __forceinline__ double minres_tree(double acc, double* part) {
-#pragma unroll
-    for (int s = 1; s < 64; s <<= 1) acc += __shfl_xor(acc, s, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    return ((part[0] + part[1]) + part[2]) + part[3];
-}
 // What the MINRES apply launch (knot_minres.h) does on top of the operator: y -= (beta/oldb) r1 from the second iteration on, and the
 // knot's partial of v . y.  The operator itself instantiates the body without it: not an instruction more.
 struct KktDot {
@@ -1495,8 +1416,8 @@ struct KktDot {
     double* part;            // [batch][N]
 };
 template <bool DOT> __device__ __forceinline__ void kkt_times_body(const KktArgs& a, double* lds, const KktDot& d, double* tree) {
-    constexpr int WG = JP_WG, JB = JP_BLOCK_CAP / WG, LQ = LG_LAM_CAP / WG, RQ = JP_ROW_CAP / WG, HB = KK_HB;
-    static_assert(JP_BLOCK_CAP % WG == 0 && JP_OTHER_CAP <= WG && JP_GLOB_CAP <= WG && JP_V_STRIDE <= WG && LG_ENT_CAP == JP_BLOCK_CAP && WG == 256, "kkt staging by 256 threads");
+    constexpr int WG = JP_WG, RQ = JP_ROW_CAP / WG;
+    static_assert(LG_ENT_CAP == JP_BLOCK_CAP && WG == 256, "kkt staging by 256 threads: the column words address the row stage's own block");
     bool sub = false;
     double c1 = 0.0;
     if constexpr (DOT) {
@@ -1513,138 +1434,80 @@ template <bool DOT> __device__ __forceinline__ void kkt_times_body(const KktArgs
     double* jg = lds + KK_JG;
     double* hv = lds + KK_HV;
     int32_t* hw = reinterpret_cast<int32_t*>(lds + KK_HW);
+    const JacRunDims& jd = a.jd; const HessRunDims& hd = a.hd;
     const int tid = threadIdx.x;
-    const int b = blockIdx.y, k = blockIdx.x, N = a.N;
-    const int first = k == 0, last = k == N - 1;
-    const int pv = first ? PV_FIRST : (last ? PV_LAST : (k == 1 ? PV_SECOND : PV_INTERIOR));
-    const int bv = first ? VAR_FIRST : (last ? VAR_LAST : VAR_INTERIOR);
+    const int b = blockIdx.y, k = blockIdx.x, N = jd.N;
+    const int last = k == N - 1;
+    const int pv = pair_variant(k, N), bv = block_variant(k, N);
     const JprodTables& jt = *a.jt;
     const LgradTables& lt = *a.tt;
-    const HvpTables& vt = *a.vt;
-    const double* jvals = a.jvals + int64_t(b) * a.nnz;
-    const double* hvals = a.hvals + int64_t(b) * a.nnz_h;
-    const double* vb = a.v + int64_t(b) * a.n;
-    const double* wb = a.w + int64_t(b) * a.m;
+    const double* jvals = a.jvals + int64_t(b) * jd.nnz;
+    const double* vb = a.v + int64_t(b) * jd.n;
+    const double* wb = a.w + int64_t(b) * jd.m;
     const bool with_dx = a.dx != nullptr, with_dc = a.dc != nullptr;
-    auto block_len = [&](int kk) __attribute__((always_inline)) { return kk == 0 ? a.nnz_first : (kk == N - 1 ? a.nnz_last : a.nnz_interior); };
-    auto block_base = [&](int kk) __attribute__((always_inline)) { return kk == 0 ? int64_t(0) : int64_t(a.nnz_first) + int64_t(kk - 1) * a.nnz_interior; };
     const bool col_thread = tid < NXK, glob_thread = last && tid >= LG_SPAN_GLOB && tid < LG_SPAN_GLOB + NXG;
+    JacRowStage rows(tid); RecordStage rec(tid);
+    JacColumnStage<LgradTables> cols(tid); HessBlockStage<HvpTables> hs(tid);
     // ---- the table words first: the multipliers are addressed by them
-    int32_t ra[RQ], rb[RQ], dir[RQ], la[LQ], lb[LQ];
+    int32_t ra[RQ], rb[RQ], dir[RQ];
 #pragma unroll
     for (int it = 0; it < RQ; ++it) { const int q = tid + it * WG; ra[it] = jt.row_a[pv][q]; rb[it] = jt.row_b[pv][q]; dir[it] = jt.rdir[pv][q]; }
-#pragma unroll
-    for (int it = 0; it < LQ; ++it) { la[it] = lt.row_a[bv][tid + it * WG]; lb[it] = lt.row_b[bv][tid + it * WG]; }
-    // ---- the jac run: own block, predecessor's block, the extras
-    const int n_own = block_len(k), n_pred = first ? 0 : block_len(k - 1);
-    const double* own = jvals + block_base(k);
-    const double* pred = jvals + block_base(first ? 0 : k - 1);
-    double o[JB], p[JB];
-#pragma unroll
-    for (int it = 0; it < JB; ++it) { const int i = tid + it * WG; o[it] = i < n_own ? own[i] : 0.0; }
-#pragma unroll
-    for (int it = 0; it < JB; ++it) { const int i = tid + it * WG; p[it] = i < n_pred ? pred[i] : 0.0; }
-    double ex = 0.0;   // the entries of knot 0's block a last knot needs (threads 0 ..), the horizon-global run at knot 0 (threads 128 ..)
-    if (tid < JP_OTHER_CAP) {
-        const int32_t q = jt.other[tid];
-        if (last && q >= 0 && q < a.nnz_first) ex = jvals[q];
-    } else if (tid - JP_OTHER_CAP < JP_GLOB_CAP) {
-        const int i = tid - JP_OTHER_CAP;
-        if (first && i < a.nnz_glob) ex = jvals[a.glob_base + i];
-    }
-    const double og = (last && tid < 16 && tid < a.nnz_glob) ? jvals[a.glob_base + tid] : 0.0;   // the same run for the last knot's global columns
-    // ---- the records of v (own knot, predecessor, other horizon end, globals) and this thread's element of d_x
-    double v0 = 0.0, v1 = 0.0, v2 = 0.0, dxc = 0.0;
-    if (tid < JP_V_STRIDE) {
-        if (col_thread) {
-            v0 = vb[int64_t(NXK) * k + tid];
-            if (!first) v1 = vb[int64_t(NXK) * (k - 1) + tid];
-            if (last) v2 = vb[tid];
-            if (with_dx) dxc = a.dx[int64_t(b) * a.n + int64_t(NXK) * k + tid];
-        }
-    } else if (tid - JP_V_STRIDE < JP_V_WORDS - JP_V_GLOB) {
-        const int i = tid - JP_V_STRIDE;
-        if (i < NXG) v0 = vb[int64_t(NXK) * N + i];
-        if (glob_thread && with_dx) dxc = a.dx[int64_t(b) * a.n + int64_t(NXK) * N + i];
-    }
-    // ---- the entry words of rows and columns
-    int32_t wr[JP_WORDS_PER_THREAD], cw[JB];
-#pragma unroll
-    for (int it = 0; it < JP_WORDS_PER_THREAD; ++it) wr[it] = jt.word[pv][tid + it * WG];
-#pragma unroll
-    for (int it = 0; it < JB; ++it) cw[it] = lt.word[bv][tid + it * WG];
-    const int32_t cwg = lt.word[bv][LG_ENT_CAP + (tid & 15)];
-    const int32_t e0 = lt.beg[bv][tid], e1 = lt.end[bv][tid];
+    cols.issue_rows(lt, bv);
+    // ---- the jac run (own block, predecessor's block, the extras, the row entry words; the same run for the last knot's global columns, the
+    // column words), the records of v and this thread's element of d_x
+    rows.issue(jt, jd, jvals, k);
+    cols.issue(lt, bv, jd, jvals, k);
+    rec.issue(vb, k, N);
+    double dxc = 0.0;
+    if (with_dx && col_thread) dxc = a.dx[int64_t(b) * jd.n + int64_t(NXK) * k + tid];
+    else if (with_dx && glob_thread) dxc = a.dx[int64_t(b) * jd.n + int64_t(NXK) * N + (tid - LG_SPAN_GLOB)];
+    const double v0 = rec.r0;   // (stays in a register: kkt_top and the partial of v . y take it)
     // ---- the multipliers: those of the column sums, and w_i / d_c,i of the owned rows
-    double lv[LQ], wq[RQ], dcq[RQ];
-#pragma unroll
-    for (int it = 0; it < LQ; ++it) lv[it] = la[it] != G_NONE ? wb[la[it] + lb[it] * k] : 0.0;
+    cols.issue_multipliers(wb, k);
+    double wq[RQ], dcq[RQ];
 #pragma unroll
     for (int it = 0; it < RQ; ++it) {
         const bool on = ra[it] != G_NONE && with_dc;
         wq[it] = (on || (DOT && ra[it] != G_NONE)) ? wb[ra[it] + rb[it] * k] : 0.0;
-        dcq[it] = on ? a.dc[int64_t(b) * a.m + ra[it] + rb[it] * k] : 0.0;
+        dcq[it] = on ? a.dc[int64_t(b) * jd.m + ra[it] + rb[it] * k] : 0.0;
     }
     // ---- the Hessian run: the knot's block, its touch words, the coupling term of both horizon ends (held in registers across phase 1)
-    const double* blk = hvals + int64_t(a.nnz_knot) * k;
-    double h[HB];
-    int32_t hwr[HVP_WORDS_PER_THREAD];
-#pragma unroll
-    for (int it = 0; it < HB; ++it) { const int i = tid + it * WG; h[it] = i < a.nnz_knot ? blk[i] : 0.0; }
-#pragma unroll
-    for (int it = 0; it < HVP_WORDS_PER_THREAD; ++it) hwr[it] = vt.word_pos[tid + it * WG];
-    const int32_t row = vt.row[tid];
-    const bool ends_coupled = a.n_couple > 0 && (first || last);
-    double vo = 0.0, cpl = 0.0;
-    if (col_thread && ends_coupled && ((row >> HVP_COUPLED_BIT) & 1)) {
-        vo = vb[int64_t(NXK) * (first ? N - 1 : 0) + tid];
-        cpl = hvals[int64_t(a.nnz_knot) * N + vt.couple[tid]];
-    }
+    hs.issue(*a.vt, hd, a.hvals + int64_t(b) * hd.nnz_h, vb, k, N);
     // ---- phase 1: jac values, entry words, v and w -> LDS
-    if (tid < JP_V_STRIDE) { vs[tid] = v0; vs[JP_V_PRED + tid] = v1; vs[JP_V_OTHER + tid] = v2; }
-    else if (tid - JP_V_STRIDE < JP_V_WORDS - JP_V_GLOB) vs[JP_V_GLOB + (tid - JP_V_STRIDE)] = v0;
-#pragma unroll
-    for (int it = 0; it < JB; ++it) { js[tid + it * WG] = o[it]; js[JP_POS_PRED + tid + it * WG] = p[it]; lw[tid + it * WG] = cw[it]; }
-#pragma unroll
-    for (int it = 0; it < JP_WORDS_PER_THREAD; ++it) tw[tid + it * WG] = wr[it];
-#pragma unroll
-    for (int it = 0; it < LQ; ++it) ls[tid + it * WG] = lv[it];
-    if (tid < JP_OTHER_CAP + JP_GLOB_CAP) js[JP_POS_OTHER + tid] = ex;   // (JP_POS_GLOB == JP_POS_OTHER + JP_OTHER_CAP)
-    if (tid < 16) { jg[tid] = og; lw[LG_ENT_CAP + tid] = cwg; }
+    rec.land(vs, rec.r0, rec.r1, rec.r2);
+    rows.land(js, tw);
+    cols.land(lw, ls, jg);
     __syncthreads();
     // the column of J^T w (the horizon-global columns read their run from jg: the words address it from LG_ENT_CAP on)
     double jtc = 0.0;
-    if (col_thread) jtc = jprod_column_staged(false, 0.0, 0.0, e0, e1, lw, ls, js);
-    else if (glob_thread) jtc = jprod_column_staged(false, 0.0, 0.0, e0, e1, lw, ls, jg - LG_ENT_CAP);
+    if (col_thread) jtc = jprod_column_staged(false, 0.0, 0.0, cols.e0, cols.e1, lw, ls, js);
+    else if (glob_thread) jtc = jprod_column_staged(false, 0.0, 0.0, cols.e0, cols.e1, lw, ls, jg - LG_ENT_CAP);
     // the owned rows of J v, and bottom
     double yr[RQ];   // (DOT) the owned rows of y: the chain of the partial takes the top element first
     {
-        double* out = a.bottom + int64_t(b) * a.m;
+        double* out = a.bottom + int64_t(b) * jd.m;
 #pragma unroll
         for (int it = 0; it < RQ; ++it)
             if (ra[it] != G_NONE) {
                 double y = kkt_bottom(with_dc, dcq[it], wq[it], jprod_row_staged(dir[it], tw, js, vs));
-                if constexpr (DOT) yr[it] = y = minres_sub_r1(sub, c1, sub ? d.r1_bottom[int64_t(b) * a.m + ra[it] + rb[it] * k] : 0.0, y);
+                if constexpr (DOT) yr[it] = y = minres_sub_r1(sub, c1, sub ? d.r1_bottom[int64_t(b) * jd.m + ra[it] + rb[it] * k] : 0.0, y);
                 out[ra[it] + rb[it] * k] = y;
             }
     }
     __syncthreads();   // every sum over the jac values is in registers: their LDS is dead
     // ---- phase 2: the Hessian block and its touch words over it
-#pragma unroll
-    for (int it = 0; it < HB; ++it) hv[tid + it * WG] = h[it];
-#pragma unroll
-    for (int it = 0; it < HVP_WORDS_PER_THREAD; ++it) hw[tid + it * WG] = hwr[it];
+    hs.land(hv, hw);
     __syncthreads();
     double acc = 0.0;
     if (col_thread) {
-        const double y = hvp_thread_row(ends_coupled ? row : row & ~(1 << HVP_COUPLED_BIT), hw, vs, [&](int pos) __attribute__((always_inline)) { return hv[pos]; }, cpl, vo);
+        const double y = hvp_thread_row(hs.row_word(), hw, vs, [&](int pos) __attribute__((always_inline)) { return hv[pos]; }, hs.cpl, hs.vo);
         double t = kkt_top(with_dx, dxc, v0, y, jtc);
-        const int64_t i = int64_t(b) * a.n + int64_t(NXK) * k + tid;
+        const int64_t i = int64_t(b) * jd.n + int64_t(NXK) * k + tid;
         if constexpr (DOT) { t = minres_sub_r1(sub, c1, sub ? d.r1_top[i] : 0.0, t); acc = fm_fma(v0, t, acc); }
         a.top[i] = t;
     } else if (glob_thread) {   // no entry of the Hessian touches the horizon-global variables
         double t = kkt_top(with_dx, dxc, v0, 0.0, jtc);
-        const int64_t i = int64_t(b) * a.n + int64_t(NXK) * N + (tid - LG_SPAN_GLOB);
+        const int64_t i = int64_t(b) * jd.n + int64_t(NXK) * N + (tid - LG_SPAN_GLOB);
         if constexpr (DOT) { t = minres_sub_r1(sub, c1, sub ? d.r1_top[i] : 0.0, t); acc = fm_fma(v0, t, acc); }
         a.top[i] = t;
     }
@@ -1652,7 +1515,7 @@ template <bool DOT> __device__ __forceinline__ void kkt_times_body(const KktArgs
 #pragma unroll
         for (int it = 0; it < RQ; ++it)
             if (ra[it] != G_NONE) acc = fm_fma(wq[it], yr[it], acc);
-        const double s = minres_tree(acc, tree);
+        const double s = workgroup_tree(acc, tree);
         if (tid == 0) d.part[int64_t(b) * N + k] = s;
     }
 }
@@ -1730,8 +1593,7 @@ template <int K> __device__ __forceinline__ void minres_sum_staged(const double*
     for (int j = 0; j < K; ++j) sum[j] = buf[j];
 }
 __device__ __forceinline__ MinresOwned minres_owned_of(const MinresArgs& s, int tid, int k) {
-    const int pv = k == 0 ? PV_FIRST : (k == s.N - 1 ? PV_LAST : (k == 1 ? PV_SECOND : PV_INTERIOR));
-    return minres_owned(tid, k, s.N, s.jt->row_a[pv], s.jt->row_b[pv]);
+    return minres_owned(tid, k, s.N, s.jt->row_a[pair_variant(k, s.N)], s.jt->row_b[pair_variant(k, s.N)]);
 }
 
 __global__ __launch_bounds__(JP_WG)
@@ -1793,7 +1655,7 @@ void hipnlp_kkt_minres_first_kernel(MinresArgs s) {
         vec(MR_Y)[i] = ym;
         acc = fm_fma(r, ym, acc);
     }
-    const double sum = minres_tree(acc, tree);
+    const double sum = workgroup_tree(acc, tree);
     if (tid == 0) s.part_b[int64_t(b) * s.N + k] = sum;
 }
 
@@ -1875,8 +1737,8 @@ void hipnlp_kkt_minres_second_kernel(MinresArgs s) {
 // periodicity rows) and among the six globals, and the workgroup computes minv_top of all four records ITSELF — one gathered Hessian
 // value (SaddleDiagTables::diag, the block position of the variable's diagonal entry) and one d_x per thread and record; the same
 // expression on the same inputs as the owner's, so the same bits.  The Hessian block is not staged.
-//   loads: everything is requested before the first LDS write: the own and the predecessor's block of the jac run and the extras, as
-//   phase 1 of the operator; the row entry words; the diagonal entries and d_x of the records; d_c of the owned rows.
+//   loads: everything is requested before the first LDS write: the jac run and the row entry words (JacRowStage of knot_values_stage.h:
+//   the text phase 1 of the operator runs); the diagonal entries and d_x of the records; d_c of the owned rows.
 //   LDS: the four records of minv_top in the JP_V_* arrangement (where the operator keeps v), the jac values, the row entry words:
 //   42 688 B — three workgroups per CU by LDS (34 granules of 1 280 B each).
 //   behind the one barrier: the owned rows over the JprodTables words (precond_row_staged), d_c last, the reciprocal.
@@ -1896,60 +1758,43 @@ struct SaddleDiagArgs {
     double* minv_top;       // [batch][n]
     double* minv_bottom;    // [batch][m]
     double floor;
-    int32_t N, n, m, nnz_first, nnz_interior, nnz_last, nnz_glob, nnz_knot;
-    int64_t nnz, glob_base, nnz_h;
+    JacRunDims jd;
+    HessRunDims hd;
 };
 constexpr int SD_MS = 0, SD_JS = SD_MS + JP_V_WORDS, SD_TW = SD_JS + JP_VALUES, SD_WORDS = SD_TW + JP_ENT_CAP / 2;
 static_assert(3 * ((SD_WORDS * int(sizeof(double)) + 1279) / 1280) * 1280 <= 160 * 1024, "three workgroups per CU");
 __global__ __launch_bounds__(JP_WG)
 void hipnlp_saddle_diag_kernel(SaddleDiagArgs a) {
-    constexpr int WG = JP_WG, JB = JP_BLOCK_CAP / WG, RQ = JP_ROW_CAP / WG;
-    static_assert(JP_BLOCK_CAP % WG == 0 && JP_OTHER_CAP <= WG && JP_GLOB_CAP <= WG && JP_V_STRIDE <= WG && JP_V_STRIDE + (JP_V_WORDS - JP_V_GLOB) <= WG && WG == 256, "staging by 256 threads");
+    constexpr int WG = JP_WG, RQ = JP_ROW_CAP / WG;
     __shared__ alignas(16) double lds[SD_WORDS];
     double* ms = lds + SD_MS;
     double* js = lds + SD_JS;
     int32_t* tw = reinterpret_cast<int32_t*>(lds + SD_TW);
+    const JacRunDims& jd = a.jd; const HessRunDims& hd = a.hd;
     const int tid = threadIdx.x;
-    const int b = blockIdx.y, k = blockIdx.x, N = a.N;
+    const int b = blockIdx.y, k = blockIdx.x, N = jd.N;
     const int first = k == 0, last = k == N - 1;
-    const int pv = first ? PV_FIRST : (last ? PV_LAST : (k == 1 ? PV_SECOND : PV_INTERIOR));
+    const int pv = pair_variant(k, N);
     const JprodTables& jt = *a.jt;
-    const double* jvals = a.jvals + int64_t(b) * a.nnz;
-    const double* hvals = a.hvals + int64_t(b) * a.nnz_h;
+    const double* hvals = a.hvals + int64_t(b) * hd.nnz_h;
     const bool with_dx = a.dx != nullptr, with_dc = a.dc != nullptr;
-    const double* dxb = with_dx ? a.dx + int64_t(b) * a.n : nullptr;
-    auto block_len = [&](int kk) __attribute__((always_inline)) { return kk == 0 ? a.nnz_first : (kk == N - 1 ? a.nnz_last : a.nnz_interior); };
-    auto block_base = [&](int kk) __attribute__((always_inline)) { return kk == 0 ? int64_t(0) : int64_t(a.nnz_first) + int64_t(kk - 1) * a.nnz_interior; };
+    const double* dxb = with_dx ? a.dx + int64_t(b) * jd.n : nullptr;
     const bool col_thread = tid < NXK, glob_thread = tid >= JP_V_STRIDE && tid < JP_V_STRIDE + NXG;
+    JacRowStage rows(tid); RecordStage rec(tid);
     // ---- the table words
     int32_t ra[RQ], rb[RQ], dir[RQ];
 #pragma unroll
     for (int it = 0; it < RQ; ++it) { const int q = tid + it * WG; ra[it] = jt.row_a[pv][q]; rb[it] = jt.row_b[pv][q]; dir[it] = jt.rdir[pv][q]; }
     const int32_t dp = a.dt->diag[tid];
-    const bool has_diag = col_thread && dp >= 0 && dp < a.nnz_knot;
-    // ---- the jac run: own block, predecessor's block, the extras (phase 1 of the operator)
-    const int n_own = block_len(k), n_pred = first ? 0 : block_len(k - 1);
-    const double* own = jvals + block_base(k);
-    const double* pred = jvals + block_base(first ? 0 : k - 1);
-    double o[JB], p[JB];
-#pragma unroll
-    for (int it = 0; it < JB; ++it) { const int i = tid + it * WG; o[it] = i < n_own ? own[i] : 0.0; }
-#pragma unroll
-    for (int it = 0; it < JB; ++it) { const int i = tid + it * WG; p[it] = i < n_pred ? pred[i] : 0.0; }
-    double ex = 0.0;   // the entries of knot 0's block a last knot needs (threads 0 ..), the horizon-global run at knot 0 (threads 128 ..)
-    if (tid < JP_OTHER_CAP) {
-        const int32_t q = jt.other[tid];
-        if (last && q >= 0 && q < a.nnz_first) ex = jvals[q];
-    } else if (tid - JP_OTHER_CAP < JP_GLOB_CAP) {
-        const int i = tid - JP_OTHER_CAP;
-        if (first && i < a.nnz_glob) ex = jvals[a.glob_base + i];
-    }
+    const bool has_diag = col_thread && dp >= 0 && dp < hd.nnz_knot;
+    // ---- the jac run: own block, predecessor's block, the extras, the row entry words (knot_values_stage.h JacRowStage: the operator's)
+    rows.issue(jt, jd, a.jvals + int64_t(b) * jd.nnz, k);
     // ---- the diagonal entries and d_x of the records: own knot, predecessor, other horizon end; the globals have no entry
     double h0 = 0.0, h1 = 0.0, h2 = 0.0, x0 = 0.0, x1 = 0.0, x2 = 0.0;
     if (col_thread) {
         if (has_diag) {
-            h0 = hvals[int64_t(a.nnz_knot) * k + dp];
-            if (!first) h1 = hvals[int64_t(a.nnz_knot) * (k - 1) + dp];
+            h0 = hvals[int64_t(hd.nnz_knot) * k + dp];
+            if (!first) h1 = hvals[int64_t(hd.nnz_knot) * (k - 1) + dp];
             if (last) h2 = hvals[dp];
         }
         if (with_dx) {
@@ -1960,13 +1805,10 @@ void hipnlp_saddle_diag_kernel(SaddleDiagArgs a) {
     } else if (glob_thread && with_dx) {
         x0 = dxb[int64_t(NXK) * N + (tid - JP_V_STRIDE)];
     }
-    // ---- the entry words of the rows, d_c of the owned rows
-    int32_t wr[JP_WORDS_PER_THREAD];
-#pragma unroll
-    for (int it = 0; it < JP_WORDS_PER_THREAD; ++it) wr[it] = jt.word[pv][tid + it * WG];
+    // ---- d_c of the owned rows
     double dcq[RQ];
 #pragma unroll
-    for (int it = 0; it < RQ; ++it) dcq[it] = (ra[it] != G_NONE && with_dc) ? a.dc[int64_t(b) * a.m + ra[it] + rb[it] * k] : 0.0;
+    for (int it = 0; it < RQ; ++it) dcq[it] = (ra[it] != G_NONE && with_dc) ? a.dc[int64_t(b) * jd.m + ra[it] + rb[it] * k] : 0.0;
     // ---- minv_top of the records (zeros where the operator stages zeros of v), everything -> LDS
     double m0 = 0.0, m1 = 0.0, m2 = 0.0;
     if (col_thread) {
@@ -1976,23 +1818,18 @@ void hipnlp_saddle_diag_kernel(SaddleDiagArgs a) {
     } else if (glob_thread) {
         m0 = precond_top(with_dx, 0.0, x0, a.floor);
     }
-    if (tid < JP_V_STRIDE) { ms[tid] = m0; ms[JP_V_PRED + tid] = m1; ms[JP_V_OTHER + tid] = m2; }
-    else if (tid - JP_V_STRIDE < JP_V_WORDS - JP_V_GLOB) ms[JP_V_GLOB + (tid - JP_V_STRIDE)] = m0;
-#pragma unroll
-    for (int it = 0; it < JB; ++it) { js[tid + it * WG] = o[it]; js[JP_POS_PRED + tid + it * WG] = p[it]; }
-#pragma unroll
-    for (int it = 0; it < JP_WORDS_PER_THREAD; ++it) tw[tid + it * WG] = wr[it];
-    if (tid < JP_OTHER_CAP + JP_GLOB_CAP) js[JP_POS_OTHER + tid] = ex;   // (JP_POS_GLOB == JP_POS_OTHER + JP_OTHER_CAP)
+    rec.land(ms, m0, m1, m2);
+    rows.land(js, tw);
     __syncthreads();
     // ---- the owned rows, and both outputs
     {
-        double* out = a.minv_bottom + int64_t(b) * a.m;
+        double* out = a.minv_bottom + int64_t(b) * jd.m;
 #pragma unroll
         for (int it = 0; it < RQ; ++it)
             if (ra[it] != G_NONE) out[ra[it] + rb[it] * k] = precond_bottom(with_dc, dcq[it], precond_row_staged(dir[it], tw, js, ms), a.floor);
     }
-    if (col_thread) a.minv_top[int64_t(b) * a.n + int64_t(NXK) * k + tid] = m0;
-    else if (last && glob_thread) a.minv_top[int64_t(b) * a.n + int64_t(NXK) * N + (tid - JP_V_STRIDE)] = m0;
+    if (col_thread) a.minv_top[int64_t(b) * jd.n + int64_t(NXK) * k + tid] = m0;
+    else if (last && glob_thread) a.minv_top[int64_t(b) * jd.n + int64_t(NXK) * N + (tid - JP_V_STRIDE)] = m0;
 }
 
 
@@ -3594,6 +3431,12 @@ int hipnlp_eval_hess_vec_device(hipnlp_handle* h, const double* x_dev, const dou
     HIP_TRY(h, hipGetLastError());
     return HIPNLP_OK;
 }
+// the dimensions of the handle's value runs, as the stored-values kernels take them (knot_values_stage.h)
+static HessRunDims hess_run_dims(const hipnlp_handle* h) { return {h->HL.nnz_knot, h->HL.n_couple, hess_count(h)}; }
+static JacRunDims jac_run_dims(const hipnlp_handle* h) {
+    const Layout& L = h->L;
+    return {L.N, L.n, L.m, L.nnz_v[VAR_FIRST], L.nnz_v[VAR_INTERIOR], L.nnz_v[VAR_LAST], int32_t(L.jperm_glob.size()), L.nnz, L.jac_glob_base};
+}
 int hipnlp_hess_times_device(hipnlp_handle* h, const double* values_dev, const double* v_dev, double* out_dev, void* stream) {
     if (!h || !values_dev || !v_dev || !out_dev) return HIPNLP_E_INVALID;
     NOT_FRONT(h, "hipnlp_hess_times_device");
@@ -3603,7 +3446,7 @@ int hipnlp_hess_times_device(hipnlp_handle* h, const double* values_dev, const d
     HIP_TRY(h, hipSetDevice(h->dev));
     TArgs a;
     a.vt = h->d_vt; a.values = values_dev; a.v = v_dev; a.out = out_dev;
-    a.N = h->L.N; a.n = h->L.n; a.nnz_knot = h->HL.nnz_knot; a.n_couple = h->HL.n_couple; a.nnz_h = hess_count(h);
+    a.N = h->L.N; a.n = h->L.n; a.hd = hess_run_dims(h);
     hipLaunchKernelGGL(hipnlp_hess_times_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(256), 0, stream ? hipStream_t(stream) : h->stream, a);
     HIP_TRY(h, hipGetLastError());
     return HIPNLP_OK;
@@ -3650,16 +3493,13 @@ int hipnlp_jac_times_device(hipnlp_handle* h, const double* jac_values_dev, cons
     HIP_TRY(h, hipSetDevice(h->dev));
     if (dot_dev && !h->d_jdot) HIP_TRY(h, hipMalloc(&h->d_jdot, size_t(h->batch) * size_t(h->L.N) * sizeof(double)));
     hipStream_t s = stream ? hipStream_t(stream) : h->stream;
-    const Layout& L = h->L;
     JArgs a;
     a.jt = h->d_jt; a.values = jac_values_dev; a.grad = dot_dev ? grad_values_dev : nullptr; a.v = v_dev; a.jv = jv_dev; a.dot_part = dot_dev ? h->d_jdot : nullptr;
-    a.N = L.N; a.n = L.n; a.m = L.m;
-    a.nnz_first = L.nnz_v[VAR_FIRST]; a.nnz_interior = L.nnz_v[VAR_INTERIOR]; a.nnz_last = L.nnz_v[VAR_LAST]; a.nnz_glob = int32_t(L.jperm_glob.size());
-    a.nnz = L.nnz; a.glob_base = L.jac_glob_base;
+    a.jd = jac_run_dims(h);
     hipLaunchKernelGGL(hipnlp_jac_times_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(JP_WG), 0, s, a);
     HIP_TRY(h, hipGetLastError());
     if (dot_dev) {
-        hipLaunchKernelGGL(hipnlp_jac_dot_reduce_kernel, dim3(unsigned((h->batch + 63) / 64)), dim3(64), 0, s, (const double*)h->d_jdot, L.N, h->batch, dot_dev);
+        hipLaunchKernelGGL(hipnlp_jac_dot_reduce_kernel, dim3(unsigned((h->batch + 63) / 64)), dim3(64), 0, s, (const double*)h->d_jdot, h->L.N, h->batch, dot_dev);
         HIP_TRY(h, hipGetLastError());
     }
     return HIPNLP_OK;
@@ -3672,17 +3512,18 @@ int hipnlp_jac_transpose_times_device(hipnlp_handle* h, const double* jac_values
     const int rc = jprod_prepare(h, "hipnlp_jac_transpose_times_device");
     if (rc != HIPNLP_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->dev));
-    const Layout& L = h->L;
     JTArgs a;
     a.tt = h->d_jtt; a.values = jac_values_dev; a.grad = grad_values_dev; a.sigma = obj_factor_dev; a.lambda = lambda_dev; a.out = out_dev;
-    a.N = L.N; a.n = L.n; a.m = L.m;
-    a.nnz_first = L.nnz_v[VAR_FIRST]; a.nnz_interior = L.nnz_v[VAR_INTERIOR]; a.nnz_last = L.nnz_v[VAR_LAST]; a.nnz_glob = int32_t(L.jperm_glob.size());
-    a.nnz = L.nnz; a.glob_base = L.jac_glob_base;
+    a.jd = jac_run_dims(h);
     hipLaunchKernelGGL(hipnlp_jac_transpose_times_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(256), 0, stream ? hipStream_t(stream) : h->stream, a);
     HIP_TRY(h, hipGetLastError());
     return HIPNLP_OK;
 }
-// ---- the KKT operator from stored value runs (include/hipnlp.h) ---------------------------------------------------------------------------
+// ---- the KKT operator from stored value runs (include/hipnlp.h); kkt_args: its arguments on a prepared handle ------------------------------
+static KktArgs kkt_args(const hipnlp_handle* h, const double* hvals, const double* jvals, const double* dx, const double* dc, const double* v, const double* w, double* top,
+                        double* bottom) {
+    return {h->d_jt, h->d_jtt, h->d_vt, hvals, jvals, dx, dc, v, w, top, bottom, jac_run_dims(h), hess_run_dims(h)};
+}
 int hipnlp_kkt_times_device(hipnlp_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev, const double* dc_dev, const double* v_dev,
                             const double* w_dev, double* top_dev, double* bottom_dev, void* stream) {
     if (!h || !hess_values_dev || !jac_values_dev || !v_dev || !w_dev || !top_dev || !bottom_dev) return HIPNLP_E_INVALID;
@@ -3693,13 +3534,7 @@ int hipnlp_kkt_times_device(hipnlp_handle* h, const double* hess_values_dev, con
     if (const int rc = jprod_prepare(h, "hipnlp_kkt_times_device")) return rc;
     if (const int rc = hvp_prepare(h, "hipnlp_kkt_times_device")) return rc;
     HIP_TRY(h, hipSetDevice(h->dev));
-    KktArgs a;
-    a.jt = h->d_jt; a.tt = h->d_jtt; a.vt = h->d_vt; a.hvals = hess_values_dev; a.jvals = jac_values_dev; a.dx = dx_dev; a.dc = dc_dev;
-    a.v = v_dev; a.w = w_dev; a.top = top_dev; a.bottom = bottom_dev;
-    a.N = L.N; a.n = L.n; a.m = L.m;
-    a.nnz_first = L.nnz_v[VAR_FIRST]; a.nnz_interior = L.nnz_v[VAR_INTERIOR]; a.nnz_last = L.nnz_v[VAR_LAST]; a.nnz_glob = int32_t(L.jperm_glob.size());
-    a.nnz_knot = h->HL.nnz_knot; a.n_couple = h->HL.n_couple;
-    a.nnz = L.nnz; a.glob_base = L.jac_glob_base; a.nnz_h = hess_count(h);
+    const KktArgs a = kkt_args(h, hess_values_dev, jac_values_dev, dx_dev, dc_dev, v_dev, w_dev, top_dev, bottom_dev);
     hipLaunchKernelGGL(hipnlp_kkt_times_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(JP_WG), 0, stream ? hipStream_t(stream) : h->stream, a);
     HIP_TRY(h, hipGetLastError());
     return HIPNLP_OK;
@@ -3749,14 +3584,9 @@ int hipnlp_kkt_minres_device(hipnlp_handle* h, const double* hess_values_dev, co
     s.rec = reinterpret_cast<MinresRec*>(base + minres_vec_bytes(h) + 2 * minres_part_bytes(h));
     s.iterations = iterations_dev; s.residual = residual_dev; s.status = status_dev;
     s.rtol = rtol; s.N = L.N; s.n = L.n; s.m = L.m; s.batch = h->batch; s.maxit = max_iterations; s.it = 0;
-    KktArgs a;
-    a.jt = h->d_jt; a.tt = h->d_jtt; a.vt = h->d_vt; a.hvals = hess_values_dev; a.jvals = jac_values_dev; a.dx = dx_dev; a.dc = dc_dev;
-    a.v = s.vec + int64_t(MR_V) * h->batch * (int64_t(L.n) + L.m); a.w = a.v + int64_t(h->batch) * L.n;
-    a.top = s.vec + int64_t(MR_Y) * h->batch * (int64_t(L.n) + L.m); a.bottom = a.top + int64_t(h->batch) * L.n;
-    a.N = L.N; a.n = L.n; a.m = L.m;
-    a.nnz_first = L.nnz_v[VAR_FIRST]; a.nnz_interior = L.nnz_v[VAR_INTERIOR]; a.nnz_last = L.nnz_v[VAR_LAST]; a.nnz_glob = int32_t(L.jperm_glob.size());
-    a.nnz_knot = h->HL.nnz_knot; a.n_couple = h->HL.n_couple;
-    a.nnz = L.nnz; a.glob_base = L.jac_glob_base; a.nnz_h = hess_count(h);
+    double* v = s.vec + int64_t(MR_V) * h->batch * (int64_t(L.n) + L.m);
+    double* y = s.vec + int64_t(MR_Y) * h->batch * (int64_t(L.n) + L.m);
+    const KktArgs a = kkt_args(h, hess_values_dev, jac_values_dev, dx_dev, dc_dev, v, v + int64_t(h->batch) * L.n, y, y + int64_t(h->batch) * L.n);
     const dim3 grid(unsigned(h->nk), unsigned(h->batch)), wg(JP_WG);
     hipLaunchKernelGGL(hipnlp_kkt_minres_first_kernel, grid, wg, 0, st, s);
     hipLaunchKernelGGL(hipnlp_kkt_minres_second_kernel, grid, wg, 0, st, s);
@@ -3786,11 +3616,9 @@ int hipnlp_kkt_diag_precond_device(hipnlp_handle* h, const double* hess_values_d
     if (const int rc = whole_horizon_only(h, "hipnlp_kkt_diag_precond_device", "a row of g has entries in the blocks of two knots, the periodicity rows need both horizon ends")) return rc;
     if (const int rc = jprod_prepare(h, "hipnlp_kkt_diag_precond_device")) return rc;
     if (const int rc = hvp_prepare(h, "hipnlp_kkt_diag_precond_device")) return rc;   // (the Hessian layout, and that its entries stay inside a knot record)
-    const Layout& L = h->L;
-    const HessLayout& HL = h->HL;
     if (!h->d_dt) {
         SaddleDiagTables* t = new SaddleDiagTables();
-        for (int i = 0; i < JP_WG; ++i) t->diag[i] = i < NXK ? HL.hv_diag[size_t(i)] : -1;
+        for (int i = 0; i < JP_WG; ++i) t->diag[i] = i < NXK ? h->HL.hv_diag[size_t(i)] : -1;
         const int rc = upload_table(h, reinterpret_cast<void**>(&h->d_dt), t, sizeof(SaddleDiagTables), "Hessian diagonal positions");
         delete t;
         if (rc != HIPNLP_OK) return rc;
@@ -3799,10 +3627,7 @@ int hipnlp_kkt_diag_precond_device(hipnlp_handle* h, const double* hess_values_d
     SaddleDiagArgs a;
     a.jt = h->d_jt; a.dt = h->d_dt; a.hvals = hess_values_dev; a.jvals = jac_values_dev; a.dx = dx_dev; a.dc = dc_dev;
     a.minv_top = minv_top_dev; a.minv_bottom = minv_bottom_dev; a.floor = floor;
-    a.N = L.N; a.n = L.n; a.m = L.m;
-    a.nnz_first = L.nnz_v[VAR_FIRST]; a.nnz_interior = L.nnz_v[VAR_INTERIOR]; a.nnz_last = L.nnz_v[VAR_LAST]; a.nnz_glob = int32_t(L.jperm_glob.size());
-    a.nnz_knot = HL.nnz_knot;
-    a.nnz = L.nnz; a.glob_base = L.jac_glob_base; a.nnz_h = hess_count(h);
+    a.jd = jac_run_dims(h); a.hd = hess_run_dims(h);
     hipLaunchKernelGGL(hipnlp_saddle_diag_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(JP_WG), 0, stream ? hipStream_t(stream) : h->stream, a);
     HIP_TRY(h, hipGetLastError());
     return HIPNLP_OK;

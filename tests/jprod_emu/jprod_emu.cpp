@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../hippopt_amd/csrc/layout.h"
+#include "../values_stage_emu.h"
 
 using namespace hipnlp;
 
@@ -125,23 +126,10 @@ void jpemu_jac_times(const jpemu_handle* h, const double* values, const double* 
     std::vector<double> part(static_cast<size_t>(N), 0.0);
     std::vector<double> js(JP_VALUES), vs(JP_V_WORDS);
     for (int k = 0; k < N; ++k) {
-        const int pv = L.pair_variant_of(k), first = k == 0, last = k == N - 1;
-        const int nnz_own = L.nnz_v[L.variant_of(k)], nnz_pred = first ? 0 : L.nnz_v[L.variant_of(k - 1)];
-        // staging, as the workgroup does it (zeros where a guard keeps a load from happening)
-        std::fill(js.begin(), js.end(), 0.0);
-        std::fill(vs.begin(), vs.end(), 0.0);
-        for (int i = 0; i < JP_BLOCK_CAP; ++i) {
-            js[size_t(i)] = i < nnz_own ? values[L.jac_base(k) + i] : 0.0;
-            js[size_t(JP_POS_PRED + i)] = i < nnz_pred ? values[L.jac_base(k - 1) + i] : 0.0;
-        }
-        for (int i = 0; i < JP_OTHER_CAP; ++i) js[size_t(JP_POS_OTHER + i)] = (last && T.other[i] >= 0) ? values[L.jac_base(0) + T.other[i]] : 0.0;
-        for (int i = 0; i < JP_GLOB_CAP; ++i) js[size_t(JP_POS_GLOB + i)] = (first && i < int(L.jperm_glob.size())) ? values[L.jac_glob_base + i] : 0.0;
-        for (int i = 0; i < NXK; ++i) {
-            vs[size_t(i)] = v[long(NXK) * k + i];
-            vs[size_t(JP_V_PRED + i)] = first ? 0.0 : v[long(NXK) * (k - 1) + i];
-            vs[size_t(JP_V_OTHER + i)] = last ? v[i] : 0.0;
-        }
-        for (int i = 0; i < NXG; ++i) vs[size_t(JP_V_GLOB + i)] = v[long(NXK) * N + i];
+        const int pv = L.pair_variant_of(k);
+        // staging, as the workgroup does it (tests/values_stage_emu.h)
+        values_stage_emu::stage_jac_rows(L, T, values, k, js.data());
+        values_stage_emu::stage_records_of(v, k, N, vs.data());
         if (jv)
             for (int q = 0; q < JP_ROW_CAP; ++q) {
                 if (T.row_a[pv][q] == G_NONE) continue;
@@ -174,14 +162,11 @@ void jpemu_jac_transpose_times(const jpemu_handle* h, const double* values, cons
         const int v = L.variant_of(k), last = k == N - 1;
         std::fill(js.begin(), js.end(), 0.0);
         std::fill(ls.begin(), ls.end(), 0.0);
-        std::fill(w.begin(), w.end(), -1);
         for (int i = 0; i < LG_ENT_CAP; ++i) js[size_t(i)] = i < L.nnz_v[v] ? values[L.jac_base(k) + i] : 0.0;
         for (size_t q = 0; q < L.lg_rows[v].size(); ++q) ls[q] = lambda[L.lg_rows[v][q].first + L.lg_rows[v][q].second * k];
-        for (size_t e = 0; e < L.lg_ent[v].size(); ++e) w[e] = int32_t(L.jt_pos[v][e] | (L.lg_ent[v][e].lam << LG_SLOT_BITS));
-        if (last) {
+        values_stage_emu::stage_column_words(L, v, last, w.data());
+        if (last)
             for (size_t i = 0; i < L.jperm_glob.size(); ++i) js[LG_ENT_CAP + i] = values[L.jac_glob_base + long(i)];
-            for (size_t e = 0; e < L.lg_glob.size(); ++e) w[LG_ENT_CAP + e] = int32_t((LG_ENT_CAP + L.jt_gpos[e]) | (L.lg_glob[e].lam << LG_SLOT_BITS));
-        }
         for (int c = 0; c < NXK; ++c)
             store(long(NXK) * k + c, jprod_column_staged(grad != nullptr, sigma, grad ? grad[long(NXK) * k + c] : 0.0, L.lg_cbeg[v][size_t(c)], L.lg_cbeg[v][size_t(c) + 1], w.data(), ls.data(), js.data()));
         if (last)   // the global variables carry no cost

@@ -1,39 +1,19 @@
 """ctypes access to the TEST-ONLY CPU emulation of the stored-values Jacobian products (tests/jprod_emu)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+import emu_build
+from emu_build import dp as _dp, ip as _ip, lp as _lp
 from hippopt_amd import _abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = os.path.join(ROOT, "tests", "_build", "libhipnlp_jprod_emu.so")
-SRC = [os.path.join(ROOT, "tests", "jprod_emu", "jprod_emu.cpp")] + [
-    os.path.join(ROOT, "hippopt_amd", "csrc", f) for f in ("layout.h", "knot_body.h", "knot_jprod.h", "knot_lgrad.h", "nlp_defs.h", "knot_tanh.h")] + [
-    os.path.join(ROOT, "include", "hipnlp.h")]
+SO = emu_build.library("jprod_emu")
+SRC = emu_build.sources("jprod_emu")
 NXK = 189
 
 
 def build():
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        os.makedirs(os.path.dirname(SO), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-Wno-unused-variable", "-Wno-missing-field-initializers",
-                               "-o", SO + ".tmp", SRC[0]])
-        os.replace(SO + ".tmp", SO)
-    return SO
-
-
-def _dp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double)) if a is not None else None
-
-
-def _ip(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int)) if a is not None else None
-
-
-def _lp(a):
-    return a.ctypes.data_as(C.POINTER(C.c_long))
+    return emu_build.build(SO, SRC)
 
 
 class JprodEmu:

@@ -10,6 +10,7 @@
 #include "../../hippopt_amd/csrc/knot_hess_layout.h"
 #include "../../hippopt_amd/csrc/knot_kkt.h"
 #include "../../hippopt_amd/csrc/layout.h"
+#include "../values_stage_emu.h"
 
 using namespace hipnlp;
 
@@ -61,31 +62,15 @@ void kktemu_times(const kktemu_handle* h, const double* hess, const double* jac,
     auto store_top = [&](long i, double y) { top[i] = y; top_writes[i]++; };
     for (int k = 0; k < N; ++k) {
         const int pv = L.pair_variant_of(k), bv = L.variant_of(k), first = k == 0, last = k == N - 1;
-        const int nnz_own = L.nnz_v[bv], nnz_pred = first ? 0 : L.nnz_v[L.variant_of(k - 1)];
-        // phase 1 staging, as the workgroup does it (zeros where a guard keeps a load from happening)
-        std::fill(js.begin(), js.end(), 0.0);
-        std::fill(vs.begin(), vs.end(), 0.0);
+        // phase 1 staging, as the workgroup does it (tests/values_stage_emu.h)
+        values_stage_emu::stage_jac_rows(L, T, jac, k, js.data());
+        values_stage_emu::stage_records_of(v, k, N, vs.data());
+        values_stage_emu::stage_column_words(L, bv, last, lw.data());
         std::fill(ls.begin(), ls.end(), 0.0);
         std::fill(jg.begin(), jg.end(), 0.0);
-        std::fill(lw.begin(), lw.end(), -1);
-        for (int i = 0; i < JP_BLOCK_CAP; ++i) {
-            js[size_t(i)] = i < nnz_own ? jac[L.jac_base(k) + i] : 0.0;
-            js[size_t(JP_POS_PRED + i)] = i < nnz_pred ? jac[L.jac_base(k - 1) + i] : 0.0;
-        }
-        for (int i = 0; i < JP_OTHER_CAP; ++i) js[size_t(JP_POS_OTHER + i)] = (last && T.other[i] >= 0) ? jac[L.jac_base(0) + T.other[i]] : 0.0;
-        for (int i = 0; i < JP_GLOB_CAP; ++i) js[size_t(JP_POS_GLOB + i)] = (first && i < int(L.jperm_glob.size())) ? jac[L.jac_glob_base + i] : 0.0;
-        for (int i = 0; i < NXK; ++i) {
-            vs[size_t(i)] = v[long(NXK) * k + i];
-            vs[size_t(JP_V_PRED + i)] = first ? 0.0 : v[long(NXK) * (k - 1) + i];
-            vs[size_t(JP_V_OTHER + i)] = last ? v[i] : 0.0;
-        }
-        for (int i = 0; i < NXG; ++i) vs[size_t(JP_V_GLOB + i)] = v[long(NXK) * N + i];
         for (size_t q = 0; q < L.lg_rows[bv].size(); ++q) ls[q] = w[L.lg_rows[bv][q].first + L.lg_rows[bv][q].second * k];
-        for (size_t e = 0; e < L.lg_ent[bv].size(); ++e) lw[e] = int32_t(L.jt_pos[bv][e] | (L.lg_ent[bv][e].lam << LG_SLOT_BITS));
-        if (last) {   // the horizon-global run for the last knot's global columns: addressed from LG_ENT_CAP on
+        if (last)   // the horizon-global run for the last knot's global columns: addressed from LG_ENT_CAP on
             for (size_t i = 0; i < L.jperm_glob.size(); ++i) jg[LG_ENT_CAP + i] = jac[L.jac_glob_base + long(i)];
-            for (size_t e = 0; e < L.lg_glob.size(); ++e) lw[LG_ENT_CAP + e] = int32_t((LG_ENT_CAP + L.jt_gpos[e]) | (L.lg_glob[e].lam << LG_SLOT_BITS));
-        }
         // the owned rows of J v, and bottom
         for (int q = 0; q < JP_ROW_CAP; ++q) {
             if (T.row_a[pv][q] == G_NONE) continue;

@@ -33,24 +33,11 @@ void kpcemu_build(const kktemu_handle* h, const double* hess, const double* jac,
     };
     auto glob_of = [&](int c) { return precond_top(dx != nullptr, 0.0, dx ? dx[long(NXK) * N + c] : 0.0, floor); };
     for (int k = 0; k < N; ++k) {
-        const int pv = L.pair_variant_of(k), bv = L.variant_of(k), first = k == 0, last = k == N - 1;
-        const int nnz_own = L.nnz_v[bv], nnz_pred = first ? 0 : L.nnz_v[L.variant_of(k - 1)];
-        // the records of minv_top in the JP_V_* arrangement (zeros where a guard keeps the workgroup from computing one)
-        std::fill(ms.begin(), ms.end(), 0.0);
-        for (int i = 0; i < NXK; ++i) {
-            ms[size_t(i)] = top_of(k, i);
-            ms[size_t(JP_V_PRED + i)] = first ? 0.0 : top_of(k - 1, i);
-            ms[size_t(JP_V_OTHER + i)] = last ? top_of(0, i) : 0.0;
-        }
-        for (int i = 0; i < NXG; ++i) ms[size_t(JP_V_GLOB + i)] = glob_of(i);
-        // the jac values: phase 1 of the operator's staging
-        std::fill(js.begin(), js.end(), 0.0);
-        for (int i = 0; i < JP_BLOCK_CAP; ++i) {
-            js[size_t(i)] = i < nnz_own ? jac[L.jac_base(k) + i] : 0.0;
-            js[size_t(JP_POS_PRED + i)] = i < nnz_pred ? jac[L.jac_base(k - 1) + i] : 0.0;
-        }
-        for (int i = 0; i < JP_OTHER_CAP; ++i) js[size_t(JP_POS_OTHER + i)] = (last && T.other[i] >= 0) ? jac[L.jac_base(0) + T.other[i]] : 0.0;
-        for (int i = 0; i < JP_GLOB_CAP; ++i) js[size_t(JP_POS_GLOB + i)] = (first && i < int(L.jperm_glob.size())) ? jac[L.jac_glob_base + i] : 0.0;
+        const int pv = L.pair_variant_of(k);
+        // the records of minv_top in the JP_V_* arrangement (zeros where a guard keeps the workgroup from computing one), and the jac values
+        // as the operator's emulation stages them (tests/values_stage_emu.h)
+        values_stage_emu::stage_records(k, N, ms.data(), top_of, glob_of);
+        values_stage_emu::stage_jac_rows(L, T, jac, k, js.data());
         // the stores, thread by thread: what minres_owned gives the thread
         for (int tid = 0; tid < JP_WG; ++tid) {
             const MinresOwned o = minres_owned(tid, k, N, T.row_a[pv], T.row_b[pv]);

@@ -1,30 +1,23 @@
 """ctypes access to the TEST-ONLY CPU emulation of the device-built diagonal preconditioner of the KKT solve (tests/kkt_precond_emu)."""
 import collections
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-import kkt_minres_emu_lib
+import emu_build
+from emu_build import dp as _dp, ip as _ip
 from hippopt_amd import _abi
-from kkt_emu_lib import NXK, _dp, _ip
+from kkt_emu_lib import NXK
 from kkt_minres_emu_lib import KktMinresEmu
 
-ROOT = kkt_minres_emu_lib.ROOT
-SO = os.path.join(ROOT, "tests", "_build", "libhipnlp_kkt_precond_emu.so")
-SRC = [os.path.join(ROOT, "tests", "kkt_precond_emu", "kkt_precond_emu.cpp"), os.path.join(ROOT, "hippopt_amd", "csrc", "knot_kkt_precond.h")] + kkt_minres_emu_lib.SRC
+SO = emu_build.library("kkt_precond_emu")
+SRC = emu_build.sources("kkt_precond_emu", "kkt_minres_emu", "kkt_emu")
 
 Diagonal = collections.namedtuple("Diagonal", "top bottom top_writes bottom_writes")
 
 
 def build():
-    if not os.path.exists(SO) or any(os.path.getmtime(s) > os.path.getmtime(SO) for s in SRC):
-        os.makedirs(os.path.dirname(SO), exist_ok=True)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wextra", "-Wno-unused-variable", "-Wno-missing-field-initializers",
-                               "-o", SO + ".tmp", SRC[0]])
-        os.replace(SO + ".tmp", SO)
-    return SO
+    return emu_build.build(SO, SRC)
 
 
 class KktPrecondEmu(KktMinresEmu):
