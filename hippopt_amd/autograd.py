@@ -44,6 +44,9 @@ The static pose finder, a batch of B independent poses, has the same interface a
     gx = nlp.lagrangian_gradient(x, sigma, lam)            # ONE launch (hipnlp_pose_eval_lagrangian_grad_device)
     dot, jv = nlp.jacobian_vector_product(x, v)            # grad f . v [B], J v [B, m], ONE launch (hipnlp_pose_eval_jac_vec_device)
     hv = nlp.hessian_vector_product(x, sigma, lam, v)      # ONE launch (hipnlp_pose_eval_hess_vec_device)
+    K = nlp.kkt(x, sigma, lam, dx, dc)                     # PoseKKTValues: the two value runs (two evaluation launches)
+    top, bottom = K.matvec(v, w)                           # ONE launch (hipnlp_pose_kkt_times_device)
+    z = K.solve(b_top, b_bottom, minv="diagonal")          # the WHOLE MINRES solve in ONE launch (hipnlp_pose_kkt_minres_device); z.status
 
 A pose is one workgroup, which holds all of jac g and of the Hessian in LDS: the derivatives of the Lagrangian gradient with respect to
 sigma and lam, grad f . w and J w, are one launch too, so a double backward through any loss in f and g — (f ** 2).sum() + (g ** 2).sum()
@@ -326,6 +329,108 @@ class KKTValues:
 KKTSolution = collections.namedtuple("KKTSolution", "top bottom iterations residual status")
 
 
+class PoseKKTValues:
+    """The KKT operator of an interior-point step of every pose at one (x, sigma, lam),
+
+        K = [ H + diag dx    J^T      ]
+            [ J             -diag dc  ]
+
+    on the value runs `hess` [batch, nnz_h] (hipnlp_pose_eval_hess_device) and `jac` [batch, nnz] (hipnlp_pose_eval_device) of nlp's own
+    handle; dx [batch, 81] and dc [batch, m] are the primal-dual diagonals (None: left out).  A pose is one workgroup, which holds both
+    runs in LDS: matvec, diagonal_preconditioner and a WHOLE solve are one launch each, with no workspace — solves on different streams
+    are independent.  Not recorded by autograd."""
+
+    MAX_ITERATIONS = 4096   # what one launch may run (hipnlp_pose_kkt_minres_device)
+
+    def __init__(self, nlp, hess, jac, dx=None, dc=None):
+        self.nlp, self.hess, self.jac = nlp, hess, jac
+        nlp._check("hessian values", hess, (nlp.batch, nlp.hess_nnz))
+        nlp._check("jacobian values", jac, (nlp.batch, nlp.engine.nnz))
+        if dx is not None:
+            nlp._check("dx", dx, (nlp.batch, nlp.n))
+        if dc is not None:
+            nlp._check("dc", dc, (nlp.batch, nlp.m))
+        self.dx, self.dc = dx, dc
+
+    def _diagonals(self):
+        return dict(dx_ptr=self.dx.data_ptr() if self.dx is not None else 0, dc_ptr=self.dc.data_ptr() if self.dc is not None else 0)
+
+    def with_diagonals(self, dx=None, dc=None):
+        """the operator on the same value runs with the diagonals dx [batch, 81] and dc [batch, m] (None: left out); no launch"""
+        return PoseKKTValues(self.nlp, self.hess, self.jac, dx, dc)
+
+    def matvec(self, v, w):
+        """(top [batch, 81], bottom [batch, m]) = K [v; w], v [batch, 81], w [batch, m]; one launch (hipnlp_pose_kkt_times_device)"""
+        torch, nlp = _torch(), self.nlp
+        nlp._check("v", v, (nlp.batch, nlp.n))
+        nlp._check("w", w, (nlp.batch, nlp.m))
+        top = torch.empty_like(v, memory_format=torch.contiguous_format)
+        bottom = torch.empty_like(w, memory_format=torch.contiguous_format)
+        nlp._on_current_stream(lambda s: nlp.engine.kkt_times_device(self.hess.data_ptr(), self.jac.data_ptr(), v.data_ptr(), w.data_ptr(), top.data_ptr(), bottom.data_ptr(),
+                                                                     stream=s, **self._diagonals()))
+        return top, bottom
+
+    def diagonal_preconditioner(self, floor=1e-10):
+        """(top [batch, 81], bottom [batch, m]), ready for solve(minv=...): top = 1 / max(|diag H + dx|, floor) (diag H = 0 where the
+        pattern has no diagonal entry) and bottom = 1 / max(|dc + sum_e J_ie^2 top_col(e)|, floor), one launch
+        (hipnlp_pose_kkt_diag_precond_device).  floor > 0 keeps the reciprocals finite; its default is a guess nobody has tuned.  A NaN or
+        an infinity in the value runs or diagonals comes out as NaN (solve: status 2).  solve(minv="diagonal") builds the same diagonal
+        inside the solve's own launch."""
+        torch, nlp = _torch(), self.nlp
+        floor = _checked_floor(floor)
+        top = torch.empty((nlp.batch, nlp.n), dtype=torch.float64, device=self.hess.device)
+        bottom = torch.empty((nlp.batch, nlp.m), dtype=torch.float64, device=self.hess.device)
+        nlp._on_current_stream(lambda s: nlp.engine.kkt_diag_precond_device(self.hess.data_ptr(), self.jac.data_ptr(), top.data_ptr(), bottom.data_ptr(), floor=floor,
+                                                                            stream=s, **self._diagonals()))
+        return top, bottom
+
+    def solve(self, rhs_top, rhs_bottom, rtol=1e-8, maxiter=400, minv=None, floor=1e-10):
+        """KKTSolution(top [batch, 81], bottom [batch, m], iterations [batch] int32, residual [batch], status [batch] int32) of
+        K [top; bottom] = [rhs_top; rhs_bottom] by preconditioned MINRES from a zero start: ONE launch for the whole solve
+        (hipnlp_pose_kkt_minres_device), every pose iterating in its own workgroup until it has a status.  minv: None (the identity), a
+        pair (top [batch, 81], bottom [batch, m]) of positive diagonals, or the string "diagonal": diagonal_preconditioner(floor) built
+        inside the same launch (the same bits as passing the pair).  status 0: residual <= rtol, the relative residual in the M^-1 norm;
+        1: maxiter (at most 4096) reached; 2: breakdown (minv not positive, or data that is not finite).  Not recorded by autograd.
+        Measured with the CPU emulation of this launch (rtol 1e-8, dx and dc in U[1, 2] — not an interior-point method's): the real
+        value runs of three poses of each of six settings variants, cond(K) 1e3 to 5e6, converge with minv="diagonal" in 75 to 349
+        iterations, all eighteen; timings: profiles/r14_pose_kkt.txt."""
+        torch, nlp = _torch(), self.nlp
+        nlp._check("rhs_top", rhs_top, (nlp.batch, nlp.n))
+        nlp._check("rhs_bottom", rhs_bottom, (nlp.batch, nlp.m))
+        if not (isinstance(rtol, numbers.Real) and rtol >= 0.0):
+            raise ValueError("rtol: a real number >= 0, not %r" % (rtol,))
+        if not (isinstance(maxiter, numbers.Integral) and not isinstance(maxiter, bool) and 0 <= maxiter <= self.MAX_ITERATIONS):
+            raise ValueError("maxiter: an integer in 0 .. %d (one launch runs them all), not %r" % (self.MAX_ITERATIONS, maxiter))
+        floor = _checked_floor(floor)
+        mt = mb = None
+        build = isinstance(minv, str)
+        if build:
+            if minv != "diagonal":
+                raise ValueError('minv: a pair (top [batch, n], bottom [batch, m]), "diagonal" or None, not %r' % (minv,))
+        elif minv is not None:
+            if not (isinstance(minv, (tuple, list)) and len(minv) == 2):
+                raise TypeError('minv: a pair (top [batch, n], bottom [batch, m]), "diagonal" or None')
+            mt, mb = minv
+            nlp._check("minv top", mt, (nlp.batch, nlp.n))
+            nlp._check("minv bottom", mb, (nlp.batch, nlp.m))
+        top = torch.empty_like(rhs_top, memory_format=torch.contiguous_format)
+        bottom = torch.empty_like(rhs_bottom, memory_format=torch.contiguous_format)
+        iterations = torch.empty((nlp.batch,), dtype=torch.int32, device=nlp.device)
+        status = torch.empty((nlp.batch,), dtype=torch.int32, device=nlp.device)
+        residual = torch.empty((nlp.batch,), dtype=torch.float64, device=nlp.device)
+        nlp._on_current_stream(lambda s: nlp.engine.kkt_minres_device(
+            self.hess.data_ptr(), self.jac.data_ptr(), rhs_top.data_ptr(), rhs_bottom.data_ptr(), top.data_ptr(), bottom.data_ptr(), iterations.data_ptr(),
+            residual.data_ptr(), status.data_ptr(), minv_top_ptr=mt.data_ptr() if mt is not None else 0, minv_bottom_ptr=mb.data_ptr() if mb is not None else 0,
+            build_diagonal=build, floor=floor, rtol=float(rtol), max_iterations=int(maxiter), stream=s, **self._diagonals()))
+        return KKTSolution(top, bottom, iterations, residual, status)
+
+
+def _checked_floor(floor):
+    if not (isinstance(floor, numbers.Real) and not isinstance(floor, bool) and 0.0 < floor < float("inf")):
+        raise ValueError("floor: a finite real number > 0, not %r" % (floor,))
+    return float(floor)
+
+
 class _DeviceNLP:
     """what the two NLPs share: an engine handle on cuda:`device_index` with batch, n, m, np; tensors checked to be float64, contiguous and
     on that device; launches ordered on torch.cuda.current_stream()"""
@@ -506,6 +611,27 @@ class PoseNLP(_DeviceNLP):
         self._check("lam", lam, (self.batch, self.m))
         self._check("v", v, (self.batch, self.n))
         return self._launch_hvp(x, sigma, lam, v)
+
+    @property
+    def hess_nnz(self):
+        """entries of the lower triangle of the Hessian of the Lagrangian (engine.hess_sparsity())"""
+        if getattr(self, "_hess_nnz", None) is None:
+            self._hess_nnz = int(self.engine.hess_sparsity()[0].size)
+        return self._hess_nnz
+
+    def kkt(self, x, sigma, lam, dx=None, dc=None):
+        """PoseKKTValues at (x, sigma, lam) with the diagonals dx [batch, 81] and dc [batch, m] (None: left out): two evaluation launches
+        (hipnlp_pose_eval_device for jac g, hipnlp_pose_eval_hess_device) whose value runs it keeps; .matvec(v, w),
+        .diagonal_preconditioner() and .solve(rhs_top, rhs_bottom) are one launch each.  Not recorded by autograd."""
+        torch = _torch()
+        self._check("x", x, (self.batch, self.n))
+        sigma = self._sigma(sigma)
+        self._check("lam", lam, (self.batch, self.m))
+        jac = torch.empty(self.batch, self.engine.nnz, dtype=torch.float64, device=self.device)
+        hess = torch.empty(self.batch, self.hess_nnz, dtype=torch.float64, device=self.device)
+        self._on_current_stream(lambda s: self.engine.eval_device(x.data_ptr(), 0, 0, 0, jac.data_ptr(), stream=s))
+        self._on_current_stream(lambda s: self.engine.eval_hess_device(x.data_ptr(), sigma.data_ptr(), lam.data_ptr(), hess.data_ptr(), stream=s))
+        return PoseKKTValues(self, hess, jac, dx, dc)
 
     # ---- internals ------------------------------------------------------------------------------------------------------------------
     def _forward(self, x, f, g):

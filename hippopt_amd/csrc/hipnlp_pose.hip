@@ -536,6 +536,200 @@ void hipnlp_pose_hvp_kernel(PPArgs pa) {
     if (tid == 0) a.flags[b] = anybad;
 }
 
+// =====================================================================================================================
+// The KKT chain of a pose from STORED value runs (pose_kkt.h has the sums, the element expressions and the order of everything): the
+// operator, the diagonal preconditioner and a whole MINRES solve, ONE launch each, one workgroup of 256 threads per pose, no pose program.
+// A workgroup stages both value runs by CCS position, the three word tables and a vector record: 31.1 KB of LDS.  Every staging load is
+// requested before the first LDS store.  Thread t owns element t of the top (t < 81) and row t of the bottom (t < m).
+// =====================================================================================================================
+struct PKArgs {
+    const PoseKktTables* kt;
+    const PoseProdTables* pt;     // (its three directories)
+    const double* hess;           // [batch][hnnz]
+    const double* jac;            // [batch][nnz]
+    const double* dx;             // [batch][81]  or null
+    const double* dc;             // [batch][m]   or null
+    const double* in_top;         // [batch][81]  v (times), rhs_top (solve)
+    const double* in_bot;         // [batch][m]   w (times), rhs_bottom (solve)
+    const double* minv_top;       // [batch][81]  or null (solve: the caller's preconditioner)
+    const double* minv_bot;       // [batch][m]   or null
+    double* out_top;              // [batch][81]  top (times), minv_top (diag), sol_top (solve)
+    double* out_bot;              // [batch][m]
+    int32_t* iterations;          // [batch]      solve only
+    double* residual;             // [batch]
+    int32_t* status;              // [batch]
+    double floor, rtol;
+    int32_t maxit, build_diag, m, nnz, hnnz;
+};
+
+struct alignas(16) PoseKktLds {
+    double jac[PP_ENT_CAP];
+    double hess[PK_HESS_CAP];
+    int32_t cw[PP_ENT_CAP], rw[PP_ENT_CAP], tw[PP_TOUCH_CAP];
+    double vec[PK_VEC_WORDS];     // the vector record of the operator; minv_top while the diagonal is built
+    double part[2][4];            // the wave sums of the two trees of an iteration (pose_kkt_tree)
+};
+static_assert(sizeof(PoseKktLds) <= 32000, "five workgroups per CU by LDS (25 granules of 1 280 B)");
+static_assert(PK_WG == WG && PP_ENT_CAP % WG == 0 && PK_HESS_CAP % WG == 0 && PP_TOUCH_CAP % WG == 0, "staged by 256 threads");
+
+// the staging loads of one thread: issue() requests them all, land() writes them to LDS (no barrier here)
+struct PoseKktStage {
+    static constexpr int JB = PP_ENT_CAP / WG, HB = PK_HESS_CAP / WG, TB = PP_TOUCH_CAP / WG;
+    double j[JB], h[HB];
+    int32_t c[JB], r[JB], t[TB];
+    int32_t col_dir, row_dir, var_dir;
+    template <bool OPERATOR> __device__ __forceinline__ void issue(const PKArgs& a, int b, int tid) {
+        const double* jv = a.jac + size_t(b) * size_t(a.nnz);
+#pragma unroll
+        for (int it = 0; it < JB; ++it) { const int i = tid + it * WG; j[it] = i < a.nnz ? jv[i] : 0.0; }
+#pragma unroll
+        for (int it = 0; it < JB; ++it) r[it] = a.kt->row_word[tid + it * WG];
+        row_dir = a.pt->row_dir[tid];
+        if constexpr (OPERATOR) {
+            const double* hv = a.hess + size_t(b) * size_t(a.hnnz);
+#pragma unroll
+            for (int it = 0; it < HB; ++it) { const int i = tid + it * WG; h[it] = i < a.hnnz ? hv[i] : 0.0; }
+#pragma unroll
+            for (int it = 0; it < JB; ++it) c[it] = a.kt->col_word[tid + it * WG];
+#pragma unroll
+            for (int it = 0; it < TB; ++it) t[it] = a.kt->touch_word[tid + it * WG];
+            col_dir = a.pt->col_dir[tid];
+            var_dir = a.pt->var_dir[tid];
+        }
+    }
+    template <bool OPERATOR> __device__ __forceinline__ void land(PoseKktLds& s, int tid) const {
+#pragma unroll
+        for (int it = 0; it < JB; ++it) { s.jac[tid + it * WG] = j[it]; s.rw[tid + it * WG] = r[it]; }
+        if constexpr (OPERATOR) {
+#pragma unroll
+            for (int it = 0; it < HB; ++it) s.hess[tid + it * WG] = h[it];
+#pragma unroll
+            for (int it = 0; it < JB; ++it) s.cw[tid + it * WG] = c[it];
+#pragma unroll
+            for (int it = 0; it < TB; ++it) s.tw[tid + it * WG] = t[it];
+        }
+    }
+};
+
+// The tree of jprod_dot_tree over the workgroup's 256 per-thread chains: a butterfly over the lanes, then the four waves in order; every
+// thread returns the sum.  part: four words of LDS.  The solve calls it twice per iteration and gives the two calls DIFFERENT words
+// (PoseKktLds::part[0] and [1]): nothing separates the reads of one tree from the stores of the next tree, but between two uses of the
+// same four words lies the barrier of the other tree — no barrier of its own is needed.
+__device__ __forceinline__ double pose_kkt_tree(double acc, double* part) {
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) acc += __shfl_xor(acc, s, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    lds_barrier();
+    return ((part[0] + part[1]) + part[2]) + part[3];
+}
+
+// minv_top of this thread's variable and minv_bottom of its row (pose_kkt.h); minv_top goes through s.vec.  Ends with a barrier: s.vec is free.
+__device__ __forceinline__ void pose_kkt_diagonal(PoseKktLds& s, const PoseKktStaged& st, int tid, int m, int32_t row_dir, bool with_dx, double dx_c, bool with_dc, double dc_i,
+                                                  double h_cc, double floor, double& mt, double& mb) {
+    mt = tid < POSE_NX ? pose_kkt_minv_top(with_dx, h_cc, dx_c, floor) : 0.0;
+    if (tid < PK_BOT) s.vec[tid] = mt;
+    lds_barrier();
+    mb = tid < m ? pose_kkt_minv_bottom(st, row_dir, s.vec, with_dc, dc_i, floor) : 0.0;
+    lds_barrier();
+}
+
+__global__ __launch_bounds__(WG) void hipnlp_pose_saddle_times_kernel(PKArgs a) {
+    __shared__ PoseKktLds s;
+    const int tid = threadIdx.x, b = blockIdx.x, m = a.m;
+    const bool has_top = tid < POSE_NX, has_row = tid < m;
+    PoseKktStage stage;
+    stage.issue<true>(a, b, tid);
+    const double v = has_top ? a.in_top[size_t(b) * POSE_NX + tid] : 0.0;
+    const double w = has_row ? a.in_bot[size_t(b) * m + tid] : 0.0;
+    const double dx = (a.dx && has_top) ? a.dx[size_t(b) * POSE_NX + tid] : 0.0;
+    const double dc = (a.dc && has_row) ? a.dc[size_t(b) * m + tid] : 0.0;
+    stage.land<true>(s, tid);
+    if (tid < PK_BOT) s.vec[tid] = v;
+    s.vec[PK_BOT + tid] = w;
+    lds_barrier();
+    const PoseKktStaged st{s.jac, s.hess, s.cw, s.rw, s.tw};
+    if (has_top) a.out_top[size_t(b) * POSE_NX + tid] = pose_kkt_top(st, stage.var_dir, stage.col_dir, s.vec, a.dx != nullptr, dx, v);
+    if (has_row) a.out_bot[size_t(b) * m + tid] = pose_kkt_bottom(st, stage.row_dir, s.vec, a.dc != nullptr, dc, w);
+}
+
+__global__ __launch_bounds__(WG) void hipnlp_pose_saddle_diag_kernel(PKArgs a) {
+    __shared__ PoseKktLds s;
+    const int tid = threadIdx.x, b = blockIdx.x, m = a.m;
+    const bool has_top = tid < POSE_NX, has_row = tid < m;
+    PoseKktStage stage;
+    stage.issue<false>(a, b, tid);
+    const int32_t hd = a.kt->hdiag[tid];
+    const double dx = (a.dx && has_top) ? a.dx[size_t(b) * POSE_NX + tid] : 0.0;
+    const double dc = (a.dc && has_row) ? a.dc[size_t(b) * m + tid] : 0.0;
+    const double h_cc = (has_top && hd >= 0) ? a.hess[size_t(b) * size_t(a.hnnz) + hd] : 0.0;   // (addressed by a table word: the one load that waits for another)
+    stage.land<false>(s, tid);
+    lds_barrier();
+    const PoseKktStaged st{s.jac, s.hess, s.cw, s.rw, s.tw};
+    double mt, mb;
+    pose_kkt_diagonal(s, st, tid, m, stage.row_dir, a.dx != nullptr, dx, a.dc != nullptr, dc, h_cc, a.floor, mt, mb);
+    if (has_top) a.out_top[size_t(b) * POSE_NX + tid] = mt;
+    if (has_row) a.out_bot[size_t(b) * m + tid] = mb;
+}
+
+// The whole solve of a pose: the start, then iterations until the pose has a status — the scalars (MinresRec) are computed by every thread
+// from the same LDS words, so the loop exit is the same in every thread and every wave meets every barrier.  Per iteration: one barrier
+// behind the stores of v, one in each of the two trees.  Nothing is stored to memory before the loop has ended.
+__global__ __launch_bounds__(WG) void hipnlp_pose_saddle_solve_kernel(PKArgs a) {
+    __shared__ PoseKktLds s;
+    const int tid = threadIdx.x, b = blockIdx.x, m = a.m;
+    const bool has_top = tid < POSE_NX, has_row = tid < m;
+    PoseKktStage stage;
+    stage.issue<true>(a, b, tid);
+    const int32_t hd = a.build_diag ? a.kt->hdiag[tid] : -1;
+    const double bt = has_top ? a.in_top[size_t(b) * POSE_NX + tid] : 0.0;
+    const double bb = has_row ? a.in_bot[size_t(b) * m + tid] : 0.0;
+    const bool with_dx = a.dx != nullptr, with_dc = a.dc != nullptr;
+    const double dx = (with_dx && has_top) ? a.dx[size_t(b) * POSE_NX + tid] : 0.0;
+    const double dc = (with_dc && has_row) ? a.dc[size_t(b) * m + tid] : 0.0;
+    bool with_minv = a.minv_top != nullptr;
+    double mt = (with_minv && has_top) ? a.minv_top[size_t(b) * POSE_NX + tid] : 0.0;
+    double mb = (with_minv && has_row) ? a.minv_bot[size_t(b) * m + tid] : 0.0;
+    stage.land<true>(s, tid);
+    lds_barrier();
+    const PoseKktStaged st{s.jac, s.hess, s.cw, s.rw, s.tw};
+    if (a.build_diag) {   // (a kernel argument: the same in every thread)
+        pose_kkt_diagonal(s, st, tid, m, stage.row_dir, with_dx, dx, with_dc, dc, (has_top && hd >= 0) ? s.hess[hd] : 0.0, a.floor, mt, mb);
+        with_minv = true;
+    }
+    PoseKktElem et, eb;
+    pose_kkt_elem_start(et, bt, with_minv, mt);
+    pose_kkt_elem_start(eb, bb, with_minv, mb);
+    MinresRec rec = minres_init(pose_kkt_tree(pose_kkt_chain(has_top, et.r2, et.y, has_row, eb.r2, eb.y), s.part[1]), a.rtol, a.maxit);
+    while (__builtin_amdgcn_readfirstlane(rec.status) == MINRES_RUNNING) {
+        pose_kkt_elem_v(et, rec.beta);
+        pose_kkt_elem_v(eb, rec.beta);
+        if (has_top) s.vec[tid] = et.v;
+        if (has_row) s.vec[PK_BOT + tid] = eb.v;
+        lds_barrier();
+        const bool sub = rec.it >= 1;
+        const double c1 = sub ? minres_div(rec.beta, rec.oldb) : 0.0;
+        const double kt = has_top ? pose_kkt_top(st, stage.var_dir, stage.col_dir, s.vec, with_dx, dx, et.v) : 0.0;
+        const double kb = has_row ? pose_kkt_bottom(st, stage.row_dir, s.vec, with_dc, dc, eb.v) : 0.0;
+        pose_kkt_elem_apply(et, sub, c1, kt);
+        pose_kkt_elem_apply(eb, sub, c1, kb);
+        const double alfa = pose_kkt_tree(pose_kkt_chain(has_top, et.v, et.y, has_row, eb.v, eb.y), s.part[0]);
+        const double c2 = minres_div(alfa, rec.beta);
+        pose_kkt_elem_residual(et, c2, with_minv);
+        pose_kkt_elem_residual(eb, c2, with_minv);
+        const double sum = pose_kkt_tree(pose_kkt_chain(has_top, et.r2, et.y, has_row, eb.r2, eb.y), s.part[1]);
+        MinresStep step;
+        const MinresRec next = minres_step(rec, alfa, sum, a.rtol, a.maxit, step);
+        if (next.status != MINRES_BREAKDOWN) {   // (a breakdown leaves z as it was)
+            pose_kkt_elem_update(et, step);
+            pose_kkt_elem_update(eb, step);
+        }
+        rec = next;
+    }
+    if (has_top) a.out_top[size_t(b) * POSE_NX + tid] = et.z;
+    if (has_row) a.out_bot[size_t(b) * m + tid] = eb.z;
+    if (tid == 0) { a.iterations[b] = rec.it; a.residual[b] = rec.residual; a.status[b] = rec.status; }
+}
+
 thread_local std::string g_pose_create_error;
 
 }  // namespace
@@ -551,6 +745,9 @@ struct hipnlp_pose_handle {
     bool time_host = false;   // hipnlp_pose_set_host_timing: the host-buffer calls bracket their launch with events (each record drains the stream: ~3 us of a 25 us call)
     PoseTables* d_tb = nullptr;
     PoseProdTables* d_pt = nullptr;   // tables of the product kernels (pose_products.h): a block of their own, PoseTables is what it was
+    PoseKktTables* d_kt = nullptr;    // tables of the KKT kernels (pose_kkt.h): a third block, the other two are what they were
+    bool kkt_fits = false;            // the pattern is within what the KKT kernels stage (PoseLayout::kkt_fits)
+    std::string kkt_error;
     double *d_x = nullptr, *d_pk = nullptr, *d_xr = nullptr, *d_f = nullptr, *d_grad = nullptr, *d_g = nullptr, *d_jac = nullptr, *d_cost = nullptr;
     GParams* d_gp = nullptr;
     int32_t* d_flags = nullptr;
@@ -584,7 +781,7 @@ static void pose_free_all(hipnlp_pose_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->dev);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* dptrs[] = {h->d_tb, h->d_pt, h->d_x, h->d_pk, h->d_xr, h->d_f, h->d_grad, h->d_g, h->d_jac, h->d_cost, h->d_gp, h->d_flags, h->d_sigma, h->d_lambda, h->d_hess};
+    void* dptrs[] = {h->d_tb, h->d_pt, h->d_kt, h->d_x, h->d_pk, h->d_xr, h->d_f, h->d_grad, h->d_g, h->d_jac, h->d_cost, h->d_gp, h->d_flags, h->d_sigma, h->d_lambda, h->d_hess};
     for (void* q : dptrs) if (q) (void)hipFree(q);
     void* hptrs[] = {h->h_x, h->h_f, h->h_grad, h->h_g, h->h_jac, h->h_cost, h->h_flags, h->h_sigma, h->h_lambda, h->h_hess};
     for (void* q : hptrs) if (q) (void)hipHostFree(q);
@@ -707,6 +904,16 @@ int hipnlp_pose_create(const hipnlp_pose_desc* desc, hipnlp_pose_handle** out) {
         ce = hipnlp_internal_memcpy(h->d_pt, pt, sizeof(PoseProdTables), hipMemcpyHostToDevice);
         delete pt;
         if (ce != hipSuccess) return fail(HIPNLP_E_NODEVICE, std::string("hipMemcpy product tables: ") + hipGetErrorString(ce));
+    }
+    h->kkt_fits = h->L.kkt_fits();
+    if (!h->kkt_fits) { h->kkt_error = h->L.error; h->L.error.clear(); }   // (not an error of the handle: the three KKT entry points refuse)
+    else {
+        CREATE_TRY(hipMalloc(&h->d_kt, sizeof(PoseKktTables)));
+        PoseKktTables* kt = new PoseKktTables();
+        h->L.fill_kkt_tables(*kt);
+        ce = hipnlp_internal_memcpy(h->d_kt, kt, sizeof(PoseKktTables), hipMemcpyHostToDevice);
+        delete kt;
+        if (ce != hipSuccess) return fail(HIPNLP_E_NODEVICE, std::string("hipMemcpy KKT tables: ") + hipGetErrorString(ce));
     }
 #undef CREATE_TRY
     *out = h;
@@ -905,6 +1112,65 @@ int hipnlp_pose_eval_hess_vec_device(hipnlp_pose_handle* h, const double* x_dev,
                                      const double* v_dev, double* out_dev, void* stream) {
     if (!h || !x_dev || !obj_factor_dev || !lambda_dev || !v_dev || !out_dev) return HIPNLP_E_INVALID;
     return pose_product_launch(h, POSE_PROD_HVP, x_dev, obj_factor_dev, lambda_dev, v_dev, out_dev, nullptr, stream);
+}
+
+// ---- the KKT chain from stored value runs (pose_kkt.h): one launch each, device pointers, no host copy, no workspace ----------------------
+enum { POSE_KKT_TIMES, POSE_KKT_DIAG, POSE_KKT_SOLVE };
+static int pose_kkt_launch(hipnlp_pose_handle* h, const char* who, int which, PKArgs& a, void* stream) {
+    if (!h->kkt_fits) { h->err = std::string(who) + ": " + h->kkt_error; return HIPNLP_E_UNSUPPORTED; }
+    HIP_TRY(h, hipSetDevice(h->dev));
+    a.kt = h->d_kt; a.pt = h->d_pt;
+    a.m = h->L.m; a.nnz = h->L.nnz; a.hnnz = h->L.hnnz;
+    hipStream_t s = stream ? hipStream_t(stream) : h->stream;
+    const dim3 grid(unsigned(h->batch)), block(WG);
+    switch (which) {
+        case POSE_KKT_TIMES: hipLaunchKernelGGL(hipnlp_pose_saddle_times_kernel, grid, block, 0, s, a); break;
+        case POSE_KKT_DIAG: hipLaunchKernelGGL(hipnlp_pose_saddle_diag_kernel, grid, block, 0, s, a); break;
+        default: hipLaunchKernelGGL(hipnlp_pose_saddle_solve_kernel, grid, block, 0, s, a); break;
+    }
+    HIP_TRY(h, hipGetLastError());
+    return HIPNLP_OK;
+}
+
+int hipnlp_pose_kkt_times_device(hipnlp_pose_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* v_dev, const double* w_dev,
+                                 double* top_dev, double* bottom_dev, const double* dx_dev, const double* dc_dev, void* stream) {
+    if (!h) return HIPNLP_E_INVALID;
+    if (!hess_values_dev || !jac_values_dev || !v_dev || !w_dev || !top_dev || !bottom_dev) { h->err = "hipnlp_pose_kkt_times_device: a required pointer is null"; return HIPNLP_E_INVALID; }
+    PKArgs a{};
+    a.hess = hess_values_dev; a.jac = jac_values_dev; a.in_top = v_dev; a.in_bot = w_dev; a.out_top = top_dev; a.out_bot = bottom_dev; a.dx = dx_dev; a.dc = dc_dev;
+    return pose_kkt_launch(h, "hipnlp_pose_kkt_times_device", POSE_KKT_TIMES, a, stream);
+}
+
+int hipnlp_pose_kkt_diag_precond_device(hipnlp_pose_handle* h, const double* hess_values_dev, const double* jac_values_dev, double* minv_top_dev, double* minv_bottom_dev,
+                                        const double* dx_dev, const double* dc_dev, double floor, void* stream) {
+    if (!h) return HIPNLP_E_INVALID;
+    if (!hess_values_dev || !jac_values_dev || !minv_top_dev || !minv_bottom_dev) { h->err = "hipnlp_pose_kkt_diag_precond_device: a required pointer is null"; return HIPNLP_E_INVALID; }
+    if (!(floor > 0.0) || !minres_finite(floor)) { h->err = "hipnlp_pose_kkt_diag_precond_device: floor must be a finite number > 0"; return HIPNLP_E_INVALID; }
+    PKArgs a{};
+    a.hess = hess_values_dev; a.jac = jac_values_dev; a.out_top = minv_top_dev; a.out_bot = minv_bottom_dev; a.dx = dx_dev; a.dc = dc_dev; a.floor = floor;
+    return pose_kkt_launch(h, "hipnlp_pose_kkt_diag_precond_device", POSE_KKT_DIAG, a, stream);
+}
+
+int hipnlp_pose_kkt_minres_device(hipnlp_pose_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* rhs_top_dev, const double* rhs_bottom_dev,
+                                  double* sol_top_dev, double* sol_bottom_dev, int32_t* iterations_dev, double* residual_dev, int32_t* status_dev, const double* dx_dev,
+                                  const double* dc_dev, const double* minv_top_dev, const double* minv_bottom_dev, int build_diagonal, double floor, double rtol,
+                                  int max_iterations, void* stream) {
+    if (!h) return HIPNLP_E_INVALID;
+    if (!hess_values_dev || !jac_values_dev || !rhs_top_dev || !rhs_bottom_dev || !sol_top_dev || !sol_bottom_dev || !iterations_dev || !residual_dev || !status_dev) {
+        h->err = "hipnlp_pose_kkt_minres_device: a required pointer is null";
+        return HIPNLP_E_INVALID;
+    }
+    if (!(rtol >= 0.0) || max_iterations < 0 || max_iterations > PK_MAX_ITERATIONS || (minv_top_dev == nullptr) != (minv_bottom_dev == nullptr) ||
+        (build_diagonal && minv_top_dev) || !(floor > 0.0) || !minres_finite(floor)) {
+        h->err = "hipnlp_pose_kkt_minres_device: rtol >= 0, 0 <= max_iterations <= " + std::to_string(PK_MAX_ITERATIONS) +
+                 " (one launch runs them all), both or neither of minv_top_dev / minv_bottom_dev and neither with build_diagonal, a finite floor > 0";
+        return HIPNLP_E_INVALID;
+    }
+    PKArgs a{};
+    a.hess = hess_values_dev; a.jac = jac_values_dev; a.in_top = rhs_top_dev; a.in_bot = rhs_bottom_dev; a.out_top = sol_top_dev; a.out_bot = sol_bottom_dev;
+    a.iterations = iterations_dev; a.residual = residual_dev; a.status = status_dev; a.dx = dx_dev; a.dc = dc_dev; a.minv_top = minv_top_dev; a.minv_bot = minv_bottom_dev;
+    a.build_diag = build_diagonal != 0; a.floor = floor; a.rtol = rtol; a.maxit = max_iterations;
+    return pose_kkt_launch(h, "hipnlp_pose_kkt_minres_device", POSE_KKT_SOLVE, a, stream);
 }
 
 int hipnlp_pose_cost_terms(hipnlp_pose_handle* h, double* values) {

@@ -5,6 +5,7 @@
 
 #include "layout.h"
 #include "pose_hess_body.h"
+#include "pose_kkt.h"
 #include "pose_products.h"
 
 namespace hipnlp {
@@ -34,6 +35,7 @@ struct PoseLayout {
     std::vector<int32_t> jrowptr, jrowent;   // [m + 1], [nnz]: the CCS positions of the entries of row i, in ascending column
     std::vector<int32_t> htouchptr;          // [POSE_NX + 1] over htouch
     std::vector<HvpTouch> htouch;            // touches of variable i in CCS-position order: (position, native slot, other variable); a diagonal entry once
+    std::vector<int32_t> hdiag;              // [POSE_NX] CCS position of variable c's diagonal Hessian entry, -1 where the pattern has none (pose_kkt.h)
     std::string error;
 
     static std::string point_name(int c) { return std::string("state.contact_points.") + (c < 4 ? "left[" : "right[") + std::to_string(c % 4) + "]"; }
@@ -197,6 +199,8 @@ struct PoseLayout {
             }
             htouchptr[size_t(i) + 1] = int32_t(htouch.size());
         }
+        hdiag.assign(size_t(POSE_NX), -1);
+        for (int e = 0; e < hnnz; ++e) if (hrow[size_t(e)] == hcol[size_t(e)]) hdiag[size_t(hrow[size_t(e)])] = e;   // (build: no entry twice)
         auto too_many = [&](const char* what, long have, long cap) {
             error = std::string("the pose pattern has ") + std::to_string(have) + " " + what + ": more than the product kernels stage (" + std::to_string(cap) + ")";
             return false;
@@ -226,6 +230,28 @@ struct PoseLayout {
             t.var_dir[c] = pp_word(htouchptr[size_t(c)], htouchptr[size_t(c) + 1] - htouchptr[size_t(c)]);
         }
         for (int r = 0; r < m; ++r) t.row_dir[r] = pp_word(jrowptr[size_t(r)], jrowptr[size_t(r) + 1] - jrowptr[size_t(r)]);
+    }
+
+    // the KKT kernels (pose_kkt.h) stage both value runs by CCS position: the caps of the product kernels, which build_product_tables
+    // has checked, and PK_HESS_CAP entries of the Hessian.  A pattern beyond them is refused by the three entry points
+    // (HIPNLP_E_UNSUPPORTED), never truncated.
+    bool kkt_fits() {
+        if (nnz > PP_ENT_CAP || m > PP_ROW_CAP || long(htouch.size()) > PP_TOUCH_CAP || hnnz > PK_HESS_CAP) {
+            error = "the pose pattern (" + std::to_string(nnz) + " entries of jac g, " + std::to_string(m) + " rows, " + std::to_string(hnnz) + " entries and " +
+                    std::to_string(htouch.size()) + " touches of the Hessian) is more than the KKT kernels stage (" + std::to_string(PP_ENT_CAP) + ", " +
+                    std::to_string(PP_ROW_CAP) + ", " + std::to_string(PK_HESS_CAP) + ", " + std::to_string(PP_TOUCH_CAP) + ")";
+            return false;
+        }
+        return true;
+    }
+
+    // the device tables of the KKT kernels: the words of fill_product_tables with the CCS position as the value index, and hdiag
+    void fill_kkt_tables(PoseKktTables& t) const {
+        std::memset(&t, 0, sizeof(t));
+        for (int e = 0; e < nnz; ++e) t.col_word[e] = pp_word(e, irow[size_t(e)]);
+        for (int q = 0; q < nnz; ++q) { const int e = jrowent[size_t(q)]; t.row_word[q] = pp_word(e, jcol[size_t(e)]); }
+        for (size_t q = 0; q < htouch.size(); ++q) t.touch_word[q] = pp_word(htouch[q].pos, htouch[q].other);
+        for (int c = 0; c < PK_WG; ++c) t.hdiag[c] = c < POSE_NX ? hdiag[size_t(c)] : -1;
     }
 
     // canonical bounds (CasADi Opti canon form) of one pose from its parameter vector

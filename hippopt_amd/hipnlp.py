@@ -38,6 +38,7 @@ EXPORTS = [
     "hipnlp_pose_cost_term_name", "hipnlp_pose_num_row_blocks", "hipnlp_pose_row_block", "hipnlp_pose_last_kernel_ms", "hipnlp_pose_set_host_timing",
     "hipnlp_pose_hess_nnz", "hipnlp_pose_hess_sparsity", "hipnlp_pose_eval_hess", "hipnlp_pose_eval_hess_device",
     "hipnlp_pose_eval_lagrangian_grad_device", "hipnlp_pose_eval_jac_vec_device", "hipnlp_pose_eval_hess_vec_device",
+    "hipnlp_pose_kkt_times_device", "hipnlp_pose_kkt_diag_precond_device", "hipnlp_pose_kkt_minres_device",
     # include/hipnlp_ipopt.h: IPOPT's C callback quartet (+ eval_h) on top of the functions above
     "hipnlp_ipopt_eval_f", "hipnlp_ipopt_eval_grad_f", "hipnlp_ipopt_eval_g", "hipnlp_ipopt_eval_jac_g", "hipnlp_ipopt_eval_h",
     "hipnlp_ipopt_sizes", "hipnlp_ipopt_bounds", "hipnlp_ipopt_attach", "hipnlp_ipopt_detach", "hipnlp_ipopt_set_early_outputs",
@@ -178,6 +179,10 @@ def load_library(path=None):
         lib.hipnlp_pose_eval_lagrangian_grad_device.argtypes = [vp, vp, vp, vp, vp, vp]
         lib.hipnlp_pose_eval_jac_vec_device.argtypes = [vp, vp, vp, vp, vp, vp]
         lib.hipnlp_pose_eval_hess_vec_device.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(lib, "hipnlp_pose_kkt_times_device"):
+        lib.hipnlp_pose_kkt_times_device.argtypes = [vp] * 10
+        lib.hipnlp_pose_kkt_diag_precond_device.argtypes = [vp] * 7 + [C.c_double, vp]
+        lib.hipnlp_pose_kkt_minres_device.argtypes = [vp] * 14 + [C.c_int, C.c_double, C.c_double, C.c_int, vp]
     lib.hipnlp_hess_nnz.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.hipnlp_hess_sparsity.argtypes = [vp, ip, ip]
     lib.hipnlp_eval_hess.argtypes = [vp, dp, dp, dp, dp]
@@ -821,6 +826,36 @@ class HipPose:
         """out [batch][81] = H(x, obj_factor, lam) v, H the Hessian of eval_hess_device; H is never written"""
         vp = C.c_void_p
         self._check(self.lib.hipnlp_pose_eval_hess_vec_device(self.h, vp(x_ptr), vp(obj_factor_ptr or None), vp(lam_ptr or None), vp(v_ptr or None), vp(out_ptr or None), vp(stream or None)))
+
+    # ---- the KKT chain from stored value runs (pose_kkt.h): one launch each, one workgroup per pose, no workspace --------------------------
+    def kkt_times_device(self, hess_values_ptr, jac_values_ptr, v_ptr, w_ptr, top_ptr, bottom_ptr, dx_ptr=0, dc_ptr=0, stream=None):
+        """top [batch][81] = (H + diag dx) v + J^T w and bottom [batch][m] = J v - diag(dc) w in ONE launch (hipnlp_pose_kkt_times_device),
+        from the Hessian run [batch][nnz_h] eval_hess_device and the jac run [batch][nnz] eval_device of this handle wrote; dx and dc are
+        optional (0: that term is left out); asynchronous on `stream`; the outputs may not alias the inputs"""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_pose_kkt_times_device(self.h, vp(hess_values_ptr or None), vp(jac_values_ptr or None), vp(v_ptr or None), vp(w_ptr or None),
+                                                          vp(top_ptr or None), vp(bottom_ptr or None), vp(dx_ptr or None), vp(dc_ptr or None), vp(stream or None)))
+
+    def kkt_diag_precond_device(self, hess_values_ptr, jac_values_ptr, minv_top_ptr, minv_bottom_ptr, dx_ptr=0, dc_ptr=0, floor=1e-10, stream=None):
+        """The diagonal preconditioner of kkt_minres_device in ONE launch (hipnlp_pose_kkt_diag_precond_device): minv_top [batch][81] =
+        1 / max(|H_cc + dx_c|, floor) and minv_bottom [batch][m] = 1 / max(|dc_i + sum_e J_ie^2 minv_top_col(e)|, floor); floor > 0 (the
+        default is untuned); a NaN or an infinity of the inputs comes out as NaN"""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_pose_kkt_diag_precond_device(self.h, vp(hess_values_ptr or None), vp(jac_values_ptr or None), vp(minv_top_ptr or None),
+                                                                 vp(minv_bottom_ptr or None), vp(dx_ptr or None), vp(dc_ptr or None), float(floor), vp(stream or None)))
+
+    def kkt_minres_device(self, hess_values_ptr, jac_values_ptr, rhs_top_ptr, rhs_bottom_ptr, sol_top_ptr, sol_bottom_ptr, iterations_ptr, residual_ptr, status_ptr,
+                          dx_ptr=0, dc_ptr=0, minv_top_ptr=0, minv_bottom_ptr=0, build_diagonal=False, floor=1e-10, rtol=1e-8, max_iterations=400, stream=None):
+        """Preconditioned MINRES on the operator of kkt_times_device for every pose at once, the WHOLE solve in one launch
+        (hipnlp_pose_kkt_minres_device): sol [batch][81] / [batch][m], iterations and status (int32) and residual [batch] are device
+        pointers; diag(minv_top, minv_bottom) > 0 is optional (both 0: the identity); build_diagonal builds the diagonal of
+        kkt_diag_precond_device inside the launch (the same bits as passing its output).  Status 0 converged, 1 iteration limit
+        (max_iterations <= 4096), 2 breakdown.  No workspace: solves on different streams are independent."""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_pose_kkt_minres_device(self.h, vp(hess_values_ptr or None), vp(jac_values_ptr or None), vp(rhs_top_ptr or None), vp(rhs_bottom_ptr or None),
+                                                           vp(sol_top_ptr or None), vp(sol_bottom_ptr or None), vp(iterations_ptr or None), vp(residual_ptr or None),
+                                                           vp(status_ptr or None), vp(dx_ptr or None), vp(dc_ptr or None), vp(minv_top_ptr or None), vp(minv_bottom_ptr or None),
+                                                           1 if build_diagonal else 0, float(floor), float(rtol), int(max_iterations), vp(stream or None)))
 
     def cost_terms(self):
         names = [self.lib.hipnlp_pose_cost_term_name(i).decode() for i in range(_abi.POSE_NCOST_TERMS)]

@@ -873,6 +873,43 @@ int hipnlp_pose_eval_jac_vec_device(hipnlp_pose_handle* h, const double* x_dev, 
                                     double* gradf_dot_v_dev /*[batch] or NULL*/, double* jac_v_dev /*[batch][m] or NULL*/, void* stream);
 int hipnlp_pose_eval_hess_vec_device(hipnlp_pose_handle* h, const double* x_dev, const double* obj_factor_dev, const double* lambda_dev,
                                      const double* v_dev, double* out_dev /*[batch][81]*/, void* stream);
+/* The KKT chain of a pose from STORED value runs — hess_values_dev [batch][nnz_h] as hipnlp_pose_eval_hess_device and jac_values_dev
+ * [batch][nnz] as hipnlp_pose_eval_device of THIS handle wrote them; no pose program runs.
+ *
+ *     K = [ H + diag d_x    J^T       ]      dx_dev [batch][81], dc_dev [batch][m]: optional (NULL: that term is left out)
+ *         [ J              -diag d_c  ]
+ *
+ * A pose is one workgroup: both runs, the tables and a vector fit in its LDS, every reduction is a tree over the workgroup.  Each call
+ * is ONE launch on a grid of `batch` workgroups, enqueued on `stream` (NULL: the handle's own stream), not synchronised; there is no
+ * workspace, no reserve call and no check_every, and calls on different streams are independent.  The order of every sum is fixed
+ * (hippopt_amd/csrc/pose_kkt.h): the same bits on every launch, at every batch position.  Outputs may not alias inputs.
+ *   hipnlp_pose_kkt_times_device         top [batch][81] = (H + diag d_x) v + J^T w,  bottom [batch][m] = J v - diag(d_c) w
+ *                                        (hipnlp_kkt_times_device's combinations: top = hv + jt, with d_x one fused multiply-add on top)
+ *   hipnlp_pose_kkt_diag_precond_device  minv_top = 1 / max(|H_cc + d_x,c|, floor) (H_cc = 0 where the pattern has no diagonal entry),
+ *                                        minv_bottom = 1 / max(|d_c,i + sum_e J_ie^2 minv_top_col(e)|, floor): the arithmetic of
+ *                                        hipnlp_kkt_diag_precond_device; a NaN or an infinity of the inputs comes out as NaN
+ *   hipnlp_pose_kkt_minres_device        K [sol_top; sol_bottom] = [rhs_top; rhs_bottom] by preconditioned MINRES from a zero start, the
+ *                                        recurrence of hipnlp_kkt_minres_device, ALL iterations in the one launch.  M^-1 = diag(minv_top,
+ *                                        minv_bottom) > 0 (both NULL: the identity); build_diagonal != 0 (then both NULL) builds the
+ *                                        diagonal above inside the same launch — bit for bit the solution of calling
+ *                                        hipnlp_pose_kkt_diag_precond_device first and passing its output.  iterations_dev, status_dev
+ *                                        [batch] int32, residual_dev [batch] (phibar / beta1, the relative residual in the M^-1 norm).
+ *                                        status 0: residual <= rtol; 1: max_iterations reached; 2: breakdown (M not positive definite or
+ *                                        data that is not finite; the solution is the last one before it).
+ * HIPNLP_E_INVALID: a null handle or required pointer, floor not a finite number > 0, rtol < 0 or NaN, max_iterations < 0 or above
+ * 4096 (what one launch may run on a shared device), one of minv_top_dev / minv_bottom_dev alone, or either with build_diagonal.
+ * HIPNLP_E_UNSUPPORTED: the handle's pattern is beyond what a workgroup stages (1024 entries of jac g, 256 rows, 768 entries and 1536
+ * touches of the Hessian); nothing is truncated.  Measured: hippopt_amd/autograd.py PoseKKTValues.solve and profiles/r14_pose_kkt.txt. */
+int hipnlp_pose_kkt_times_device(hipnlp_pose_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* v_dev /*[batch][81]*/,
+                                 const double* w_dev /*[batch][m]*/, double* top_dev /*[batch][81]*/, double* bottom_dev /*[batch][m]*/,
+                                 const double* dx_dev /*or NULL*/, const double* dc_dev /*or NULL*/, void* stream);
+int hipnlp_pose_kkt_diag_precond_device(hipnlp_pose_handle* h, const double* hess_values_dev, const double* jac_values_dev, double* minv_top_dev /*[batch][81]*/,
+                                        double* minv_bottom_dev /*[batch][m]*/, const double* dx_dev /*or NULL*/, const double* dc_dev /*or NULL*/, double floor,
+                                        void* stream);
+int hipnlp_pose_kkt_minres_device(hipnlp_pose_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* rhs_top_dev,
+                                  const double* rhs_bottom_dev, double* sol_top_dev, double* sol_bottom_dev, int32_t* iterations_dev, double* residual_dev,
+                                  int32_t* status_dev, const double* dx_dev /*or NULL*/, const double* dc_dev /*or NULL*/, const double* minv_top_dev /*or NULL*/,
+                                  const double* minv_bottom_dev /*or NULL*/, int build_diagonal, double floor, double rtol, int max_iterations, void* stream);
 int hipnlp_pose_cost_terms(hipnlp_pose_handle* h, double* values /*[batch][HIPNLP_POSE_NCOST_TERMS]*/);
 const char* hipnlp_pose_cost_term_name(int i);
 int hipnlp_pose_num_row_blocks(const hipnlp_pose_handle* h);
