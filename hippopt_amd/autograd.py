@@ -47,6 +47,9 @@ The static pose finder, a batch of B independent poses, has the same interface a
     K = nlp.kkt(x, sigma, lam, dx, dc)                     # PoseKKTValues: the two value runs (two evaluation launches)
     top, bottom = K.matvec(v, w)                           # ONE launch (hipnlp_pose_kkt_times_device)
     z = K.solve(b_top, b_bottom, minv="diagonal")          # the WHOLE MINRES solve in ONE launch (hipnlp_pose_kkt_minres_device); z.status
+    F = K.factor(delta_init=1e-4, kappa=8.0, max_tries=8)  # dense L D L^T per pose with F.inertia, F.status, F.delta, F.tries: ONE launch
+    top, bottom = F.solve(b_top, b_bottom, refine=1)       #   (hipnlp_pose_kkt_ldl_device); solves from the stored factor (hipnlp_pose_kkt_ldl_solve_device)
+    top, bottom, inertia, status = K.solve_direct(b_top, b_bottom)   # factor, inertia and solve in ONE launch, no factor stored
 
 A pose is one workgroup, which holds all of jac g and of the Hessian in LDS: the derivatives of the Lagrangian gradient with respect to
 sigma and lam, grad f . w and J w, are one launch too, so a double backward through any loss in f and g — (f ** 2).sum() + (g ** 2).sum()
@@ -423,6 +426,120 @@ class PoseKKTValues:
             residual.data_ptr(), status.data_ptr(), minv_top_ptr=mt.data_ptr() if mt is not None else 0, minv_bottom_ptr=mb.data_ptr() if mb is not None else 0,
             build_diagonal=build, floor=floor, rtol=float(rtol), max_iterations=int(maxiter), stream=s, **self._diagonals()))
         return KKTSolution(top, bottom, iterations, residual, status)
+
+
+    # ---- the dense L D L^T of K per pose (hippopt_amd/csrc/pose_ldl.h): inertia, regularisation ladder, direct solves ----------------------
+    MAX_TRIES, MAX_NRHS = 16, 8   # what one launch may run (hipnlp_pose_kkt_ldl_device)
+
+    def _ladder(self, delta_init, kappa, max_tries):
+        if not (isinstance(max_tries, numbers.Integral) and not isinstance(max_tries, bool) and 0 <= max_tries <= self.MAX_TRIES):
+            raise ValueError("max_tries: an integer in 0 .. %d, not %r" % (self.MAX_TRIES, max_tries))
+        if max_tries == 0:
+            return 0.0, 0.0, 0
+        if not (isinstance(delta_init, numbers.Real) and not isinstance(delta_init, bool) and 0.0 < delta_init < float("inf")):
+            raise ValueError("delta_init: a finite real number > 0 with max_tries > 0, not %r" % (delta_init,))
+        if not (isinstance(kappa, numbers.Real) and not isinstance(kappa, bool) and 1.0 < kappa < float("inf")):
+            raise ValueError("kappa: a finite real number > 1 with max_tries > 0, not %r" % (kappa,))
+        return float(delta_init), float(kappa), int(max_tries)
+
+    def _rhs(self, rhs_top, rhs_bottom):
+        """(nrhs, whether the caller's tensors have no nrhs axis)"""
+        nlp = self.nlp
+        flat = isinstance(rhs_top, _torch().Tensor) and rhs_top.dim() == 2
+        nrhs = 1 if flat else (int(rhs_top.shape[1]) if isinstance(rhs_top, _torch().Tensor) and rhs_top.dim() == 3 else 0)
+        if not 1 <= nrhs <= self.MAX_NRHS:
+            raise ValueError("right-hand sides: [batch, 81] or [batch, nrhs, 81] with 1 <= nrhs <= %d" % self.MAX_NRHS)
+        nlp._check("rhs_top", rhs_top, (nlp.batch, nlp.n) if flat else (nlp.batch, nrhs, nlp.n))
+        nlp._check("rhs_bottom", rhs_bottom, (nlp.batch, nlp.m) if flat else (nlp.batch, nrhs, nlp.m))
+        return nrhs, flat
+
+    def _ldl(self, rhs_top, rhs_bottom, ladder, store):
+        torch, nlp = _torch(), self.nlp
+        delta_init, kappa, max_tries = ladder
+        nrhs = 0
+        top = bottom = None
+        if rhs_top is not None:
+            nrhs, _ = self._rhs(rhs_top, rhs_bottom)
+            top = torch.empty_like(rhs_top, memory_format=torch.contiguous_format)
+            bottom = torch.empty_like(rhs_bottom, memory_format=torch.contiguous_format)
+        dev = self.hess.device
+        inertia = torch.empty((nlp.batch, 3), dtype=torch.int32, device=dev)
+        status = torch.empty((nlp.batch,), dtype=torch.int32, device=dev)
+        tries = torch.empty((nlp.batch,), dtype=torch.int32, device=dev)
+        delta = torch.empty((nlp.batch,), dtype=torch.float64, device=dev)
+        factor = pivots = None
+        if store:
+            factor = torch.empty((nlp.batch, nlp.engine.kkt_ldl_doubles()), dtype=torch.float64, device=dev)
+            pivots = torch.empty((nlp.batch, nlp.n + nlp.m), dtype=torch.int32, device=dev)
+        ptr = lambda t: t.data_ptr() if t is not None else 0  # noqa: E731
+        nlp._on_current_stream(lambda s: nlp.engine.kkt_ldl_device(
+            self.hess.data_ptr(), self.jac.data_ptr(), inertia.data_ptr(), status.data_ptr(), nrhs=nrhs, rhs_top_ptr=ptr(rhs_top), rhs_bottom_ptr=ptr(rhs_bottom),
+            sol_top_ptr=ptr(top), sol_bottom_ptr=ptr(bottom), delta_ptr=delta.data_ptr(), tries_ptr=tries.data_ptr(), delta_init=delta_init, kappa=kappa, max_tries=max_tries,
+            factor_ptr=ptr(factor), pivots_ptr=ptr(pivots), stream=s, **self._diagonals()))
+        return top, bottom, inertia, status, delta, tries, factor, pivots
+
+    def factor(self, delta_init=None, kappa=8.0, max_tries=0):
+        """PoseKKTFactor: the dense L D L^T of K of every pose (Bunch-Kaufman pivoting, packed, in the pose's workgroup), ONE launch
+        (hipnlp_pose_kkt_ldl_device), with .inertia [batch, 3] int32 (positive, negative, zero eigenvalues), .status [batch] int32
+        (0 factored, 1 exactly singular, 2 data not finite, 3 ladder exhausted), .delta [batch] and .tries [batch] int32.
+        max_tries = 0: factor once, report the inertia as it is.  max_tries > 0 (at most 16): IPOPT's inertia correction on the top
+        block — try t >= 1 adds delta_init kappa^(t-1) to its diagonal — until the inertia is (81, m, 0).  Timings: profiles/r15_pose_ldl.txt."""
+        ladder = self._ladder(delta_init, kappa, max_tries)
+        _, _, inertia, status, delta, tries, factor, pivots = self._ldl(None, None, ladder, True)
+        return PoseKKTFactor(self, factor, pivots, inertia, status, delta, tries, regularised=ladder[2] > 0)
+
+    def solve_direct(self, rhs_top, rhs_bottom, delta_init=None, kappa=8.0, max_tries=0):
+        """(top, bottom, inertia [batch, 3] int32, status [batch] int32): factor (with the ladder of `factor`) and solve in ONE launch,
+        no factor stored; right-hand sides [batch, 81] / [batch, m] or [batch, nrhs, 81] / [batch, nrhs, m], nrhs <= 8.  With status 1
+        or 2 the solution is NaN; with a delta > 0 it is the solution of the regularised system."""
+        ladder = self._ladder(delta_init, kappa, max_tries)
+        top, bottom, inertia, status, _, _, _, _ = self._ldl(rhs_top, rhs_bottom, ladder, False)
+        return top, bottom, inertia, status
+
+
+class PoseKKTFactor:
+    """The stored factor of PoseKKTValues.factor: .factor [batch, N (N + 1) / 2] (packed lower triangle, N = 81 + m), .pivots [batch, N]
+    int32, .inertia [batch, 3], .status, .delta, .tries (device tensors; nothing is synchronised)."""
+
+    def __init__(self, values, factor, pivots, inertia, status, delta, tries, regularised):
+        self.values, self.factor, self.pivots = values, factor, pivots
+        self.inertia, self.status, self.delta, self.tries = inertia, status, delta, tries
+        self.regularised = regularised
+
+    def _solve(self, rhs_top, rhs_bottom, nrhs):
+        torch, nlp = _torch(), self.values.nlp
+        top = torch.empty_like(rhs_top, memory_format=torch.contiguous_format)
+        bottom = torch.empty_like(rhs_bottom, memory_format=torch.contiguous_format)
+        nlp._on_current_stream(lambda s: nlp.engine.kkt_ldl_solve_device(self.factor.data_ptr(), self.pivots.data_ptr(), nrhs, rhs_top.data_ptr(), rhs_bottom.data_ptr(),
+                                                                         top.data_ptr(), bottom.data_ptr(), stream=s))
+        return top, bottom
+
+    def solve(self, rhs_top, rhs_bottom, refine=0):
+        """(top, bottom) of K z = b from the stored factor, one launch (hipnlp_pose_kkt_ldl_solve_device); right-hand sides [batch, 81] /
+        [batch, m] or [batch, nrhs, 81] / [batch, nrhs, m], nrhs <= 8.  refine = k adds k rounds of iterative refinement composed of
+        existing launches: r = b - K z by the one-launch matvec (hipnlp_pose_kkt_times_device), a solve of r from the factor, z += it.
+        The ladder's delta is in the FACTOR only: the values' operator has their own dx.  So where a ladder was asked for, the
+        refinement runs against dx + delta — it converges to the solution of the REGULARISED system; it converges to the solution of
+        the unregularised system only where delta = 0."""
+        torch, v = _torch(), self.values
+        nrhs, flat = v._rhs(rhs_top, rhs_bottom)
+        if not (isinstance(refine, numbers.Integral) and not isinstance(refine, bool) and refine >= 0):
+            raise ValueError("refine: an integer >= 0, not %r" % (refine,))
+        top, bottom = self._solve(rhs_top, rhs_bottom, nrhs)
+        if refine:
+            op = v
+            if self.regularised:
+                dx = self.delta[:, None].expand(v.nlp.batch, v.nlp.n)
+                op = v.with_diagonals((dx if v.dx is None else v.dx + dx).contiguous(), v.dc)
+            for _ in range(int(refine)):
+                if flat:
+                    kt, kb = op.matvec(top, bottom)
+                else:
+                    prods = [op.matvec(top[:, r].contiguous(), bottom[:, r].contiguous()) for r in range(nrhs)]
+                    kt, kb = torch.stack([q[0] for q in prods], 1), torch.stack([q[1] for q in prods], 1)
+                et, eb = self._solve((rhs_top - kt).contiguous(), (rhs_bottom - kb).contiguous(), nrhs)
+                top, bottom = top + et, bottom + eb
+        return top, bottom
 
 
 def _checked_floor(floor):

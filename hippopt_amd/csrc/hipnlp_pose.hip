@@ -730,6 +730,299 @@ __global__ __launch_bounds__(WG) void hipnlp_pose_saddle_solve_kernel(PKArgs a) 
     if (tid == 0) { a.iterations[b] = rec.it; a.residual[b] = rec.residual; a.status[b] = rec.status; }
 }
 
+// =====================================================================================================================
+// The dense L D L^T of the KKT matrix of a pose (pose_ldl.h has the element expressions, the choice of the pivot and the order of
+// everything): ONE workgroup per pose holds the packed lower triangle, order 81 + m <= 176, in 127 KB of static LDS — one workgroup
+// per CU — and assembles it from the two stored value runs, factors it with Bunch-Kaufman pivoting, counts the inertia, climbs the
+// regularisation ladder and solves, all in one launch.  Nothing leaves the CU, no workgroup waits for another, every loop is bounded.
+//
+// 1 024 threads (chosen by reading, 256 and 512 UNMEASURED; DESIGN.md "Pose LDL"; timings profiles/r15_pose_ldl.txt): the trailing update is bound by LDS traffic (a read of x_i, a read and a store of
+// a_ij per fused multiply-add), one workgroup has the CU to itself, and sixteen waves — four per SIMD — keep that many LDS requests in
+// flight without unrolling; the price is a dearer barrier, four per pivot step.
+//   search   EVERY wave searches column k (and, where the diagonal does not stand, row / column imax) itself: the same LDS words,
+//            pl_max_join over its lanes — the same result in every wave, no barrier, no exchange; lanes along the column.
+//   B1       every wave has read what it searched
+//   swap     thread t owns the one pair of index t that the interchange kk <-> kp moves (B2 behind it, only where there is one)
+//   column   thread t forms the multipliers of row k + kstep + t, keeps the entry before the scaling in x0 / x1 (B3)
+//   update   columns dealt to the waves, lanes along the packed column: unit stride, no (i, j) from a linear index (B4)
+// The solves: one WAVE per right-hand side, the vector in three registers per lane, y_k by a lane broadcast: no LDS for the vector, no
+// barrier.  The backward pass reads a row of L (a stride that grows lane by lane).
+// =====================================================================================================================
+constexpr int LDL_WG = 1024, LDL_WAVES = LDL_WG / 64;
+static_assert(PL_MAX_N <= 3 * 64 && PL_MAX_NRHS <= LDL_WAVES && PL_MAX_N <= LDL_WG - 128, "a solve is one wave with three elements per lane; one thread per index");
+
+struct PLArgs {
+    const PoseLdlTables* lt;
+    const double* hess;           // [batch][hnnz]
+    const double* jac;            // [batch][nnz]
+    const double* dx;             // [batch][81]  or null
+    const double* dc;             // [batch][m]   or null
+    const double* rhs_top;        // [batch][nrhs][81]
+    const double* rhs_bot;        // [batch][nrhs][m]
+    double* sol_top;
+    double* sol_bot;
+    int32_t* inertia;             // [batch][3]
+    int32_t* status;              // [batch]
+    double* delta;                // [batch] or null
+    int32_t* tries;               // [batch] or null
+    double* factor;               // [batch][N (N + 1) / 2] or null: a destination of the factorisation, the source of the stored-factor solve
+    int32_t* pivots;              // [batch][N]
+    double delta_init, kappa;
+    int32_t max_tries, nrhs, m, nnz, hnnz;
+};
+
+struct alignas(16) PoseLdlLds {
+    double a[PL_MAX_DOUBLES];     // the packed lower triangle: K, then L and D in place
+    double x0[PL_MAX_N], x1[PL_MAX_N];   // the pivot column(s) before the scaling
+    int32_t ipiv[PL_MAX_N], perm[PL_MAX_N], kind[PL_MAX_N];   // the pivot vector; b~_i = b_perm[i]; PL_ONE / PL_FIRST / PL_SECOND
+    int32_t word[4];              // inertia and status, for the exit of the ladder
+};
+static_assert(sizeof(PoseLdlLds) <= 160 * 1024, "one workgroup per CU");
+
+__device__ __forceinline__ PlMax pose_ldl_wave_max(PlMax a) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) a = pl_max_join(a, PlMax{__shfl_xor(a.v, o, 64), __shfl_xor(a.at, o, 64), __shfl_xor(a.bad, o, 64)});
+    return a;
+}
+
+// K of one try into s.a.  Ends with a barrier.
+__device__ __forceinline__ void pose_ldl_assemble(PoseLdlLds& s, const PLArgs& a, int b, int N, int tid, bool with_dx, double dx_c, bool with_dc, double dc_i, bool with_delta,
+                                                  double delta) {
+    const int nd = pl_doubles(N);
+    for (int e = tid; e < nd; e += LDL_WG) s.a[e] = 0.0;
+    lds_barrier();
+    const double* hv = a.hess + size_t(b) * size_t(a.hnnz);
+    const double* jv = a.jac + size_t(b) * size_t(a.nnz);
+    for (int e = tid; e < a.hnnz; e += LDL_WG) s.a[a.lt->hess_at[e]] = hv[e];
+    for (int e = tid; e < a.nnz; e += LDL_WG) s.a[a.lt->jac_at[e]] = jv[e];
+    lds_barrier();
+    if (tid < POSE_NX) { const int p = pl_col(N, tid); s.a[p] = pl_diag_top(s.a[p], with_dx, dx_c, with_delta, delta); }
+    else if (tid >= 128 && tid - 128 < a.m) s.a[pl_col(N, POSE_NX + tid - 128)] = pl_diag_bottom(with_dc, dc_i);
+    lds_barrier();
+}
+
+// The factorisation of s.a in place; the status of this try.  Every thread takes every branch the same way: what it branches on comes
+// from LDS words that no thread writes between the barrier in front of the search and B1.  The caller puts a barrier behind it.
+__device__ __forceinline__ int pose_ldl_factor(PoseLdlLds& s, int N, int tid, int& pos, int& neg, int& zero) {
+    const int lane = tid & 63, wave = tid >> 6;
+    pos = neg = zero = 0;
+    if (tid < N) s.perm[tid] = tid;
+    int k = 0;
+    while (k < N) {
+        const int kc = pl_col(N, k);
+        const double akk = s.a[kc];
+        PlMax cm = pl_max_none();
+        for (int i = k + 1 + lane; i < N; i += 64) cm = pl_max_join(cm, pl_max_of(s.a[kc + i - k], i));
+        cm = pose_ldl_wave_max(cm);
+        int bad = cm.bad | (minres_finite(akk) ? 0 : 1);
+        const double absakk = pl_abs(akk), colmax = cm.v < 0.0 ? 0.0 : cm.v;
+        int kp = k, kstep = 1;
+        double arr = 0.0;
+        bool zero_column = false;
+        if (!bad) {
+            if (pl_column_is_zero(absakk, colmax)) zero_column = true;
+            else if (!pl_keep_diagonal(absakk, colmax)) {
+                const int imax = cm.at, pc = pl_col(N, imax);
+                PlMax rm = pl_max_none();
+                for (int j = k + lane; j < imax; j += 64) rm = pl_max_join(rm, pl_max_of(s.a[pl_at(N, imax, j)], j));
+                for (int i = imax + 1 + lane; i < N; i += 64) rm = pl_max_join(rm, pl_max_of(s.a[pc + i - imax], i));
+                rm = pose_ldl_wave_max(rm);
+                arr = s.a[pc];
+                bad = rm.bad | (minres_finite(arr) ? 0 : 1);
+                if (!bad) { const PlPivot pv = pl_choose(k, imax, absakk, colmax, rm.v, pl_abs(arr)); kp = pv.kp; kstep = pv.kstep; }
+            }
+        }
+        if (__builtin_amdgcn_readfirstlane(bad | int(zero_column))) {
+            if (tid >= k && tid < N) { s.ipiv[tid] = tid + 1; s.kind[tid] = PL_ONE; }
+            if (bad) return PL_NONFINITE;
+            zero = 1;
+            return PL_SINGULAR;
+        }
+        kp = __builtin_amdgcn_readfirstlane(kp);
+        kstep = __builtin_amdgcn_readfirstlane(kstep);
+        const int kk = k + kstep - 1, knc = pl_col(N, kk), base = k + kstep;
+        lds_barrier();                                                        // B1
+        if (kp != kk) {
+            if (tid < N && tid != kp) {
+                const int pcol = pl_col(N, kp);
+                int p, q;
+                if (tid < kk) { p = pl_at(N, kk, tid); q = pl_at(N, kp, tid); }          // the rows kk and kp of a column in front (and, of a 2x2 pivot, of column k)
+                else if (tid == kk) { p = knc; q = pcol; }                               // the two diagonal elements
+                else if (tid < kp) { p = knc + tid - kk; q = pl_at(N, kp, tid); }        // column kk between them against row kp
+                else { p = knc + tid - kk; q = pcol + tid - kp; }                        // the two columns below kp
+                const double u = s.a[p];
+                s.a[p] = s.a[q];
+                s.a[q] = u;
+            } else if (tid == kp) {
+                const int32_t u = s.perm[kk];
+                s.perm[kk] = s.perm[kp];
+                s.perm[kp] = u;
+            }
+            lds_barrier();                                                    // B2
+        }
+        if (kstep == 1) {
+            const double d = kp == k ? akk : arr;
+            if (d > 0.0) ++pos; else ++neg;
+            if (tid == 0) { s.ipiv[k] = kp + 1; s.kind[k] = PL_ONE; }
+            const int i = base + tid;
+            if (i < N) { const double x = s.a[kc + i - k]; s.x0[i] = x; s.a[kc + i - k] = pl_l1(x, d); }
+        } else {
+            ++pos; ++neg;
+            if (tid == 0) { s.ipiv[k] = s.ipiv[k + 1] = -(kp + 1); s.kind[k] = PL_FIRST; s.kind[k + 1] = PL_SECOND; }
+            const PlBlock blk = pl_block(s.a[kc], s.a[kc + 1], s.a[knc]);
+            const int i = base + tid;
+            if (i < N) {
+                const double x0 = s.a[kc + i - k], x1 = s.a[knc + i - kk];
+                s.x0[i] = x0; s.x1[i] = x1;
+                s.a[kc + i - k] = pl_w_first(blk, x0, x1);
+                s.a[knc + i - kk] = pl_w_second(blk, x0, x1);
+            }
+        }
+        lds_barrier();                                                        // B3
+        for (int j = base + wave; j < N; j += LDL_WAVES) {
+            const int cj = pl_col(N, j) - j;                                  // (i, j) at cj + i
+            if (kstep == 1) {
+                const double lj = s.a[kc + j - k];
+                for (int i = j + lane; i < N; i += 64) s.a[cj + i] = pl_update1(s.a[cj + i], s.x0[i], lj);
+            } else {
+                const double w0 = s.a[kc + j - k], w1 = s.a[knc + j - kk];
+                for (int i = j + lane; i < N; i += 64) s.a[cj + i] = pl_update2(s.a[cj + i], s.x0[i], s.x1[i], w0, w1);
+            }
+        }
+        lds_barrier();                                                        // B4
+        k = base;
+    }
+    return PL_OK;
+}
+
+// One right-hand side by one wave: lane l holds the elements l, l + 64, l + 128 of the vector in three named registers (no array: nothing
+// for the compiler to put into scratch memory or LDS).  good: the factor can be solved with; else the solution is NaN.  bt, bb, xt, xb: of
+// this pose and this right-hand side.  LDL_ROWS(F) states F(r, y_r, src_r) for the three elements of a lane.
+#define LDL_ROWS(F) F(0, y0, src0) F(1, y1, src1) F(2, y2, src2)
+__device__ __forceinline__ void pose_ldl_solve_wave(const PoseLdlLds& s, int N, bool good, const double* bt, const double* bb, double* xt, double* xb, int lane) {
+    double y0, y1, y2;
+    int src0, src1, src2;
+#define LDL_LOAD(r, y, src)                                                                         \
+    src = (lane + 64 * r) < N ? s.perm[lane + 64 * r] : -1;                                         \
+    y = (src >= 0 && good) ? (src < POSE_NX ? bt[src] : bb[src - POSE_NX]) : 0.0;
+    LDL_ROWS(LDL_LOAD)
+#undef LDL_LOAD
+    if (good) {
+        for (int k = 0; k < N; ++k) {                                          // forward: column k of L, (i, k) at c + i
+            const int lo = k + 1 + (s.kind[k] == PL_FIRST ? 1 : 0), c = pl_col(N, k) - k, kr = k >> 6;
+            const double yk = __shfl(kr == 0 ? y0 : (kr == 1 ? y1 : y2), k & 63, 64);
+#define LDL_FORWARD(r, y, src) { const int i = lane + 64 * r; if (i >= lo && i < N) y = pl_axpy(y, s.a[c + i], yk); }
+            LDL_ROWS(LDL_FORWARD)
+#undef LDL_FORWARD
+        }
+        // the diagonal: element i needs i + 1 (the first of a 2x2 block) or i - 1 (the second), all taken before any is changed
+        const int nl = (lane + 1) & 63, pl = (lane + 63) & 63;
+        const double n0 = __shfl(y0, nl, 64), n1 = __shfl(y1, nl, 64), n2 = __shfl(y2, nl, 64);
+        const double p0 = __shfl(y0, pl, 64), p1 = __shfl(y1, pl, 64), p2 = __shfl(y2, pl, 64);
+        const double up0 = lane == 63 ? n1 : n0, up1 = lane == 63 ? n2 : n1, up2 = n2;          // (lane 63's next element is lane 0's of the next register)
+        const double dn0 = p0, dn1 = lane == 0 ? p0 : p1, dn2 = lane == 0 ? p1 : p2;
+#define LDL_DIAGONAL(r, y, src)                                                                                                              \
+        {                                                                                                                                    \
+            const int i = lane + 64 * r;                                                                                                     \
+            if (i < N) {                                                                                                                     \
+                const int kd = s.kind[i], ci = pl_col(N, i);                                                                                 \
+                if (kd == PL_ONE) y = pl_diag1(y, s.a[ci]);                                                                                  \
+                else if (kd == PL_FIRST) y = pl_diag2_first(pl_solve_block(s.a[ci], s.a[ci + 1], s.a[pl_col(N, i + 1)]), y, up##r);          \
+                else y = pl_diag2_second(pl_solve_block(s.a[pl_col(N, i - 1)], s.a[pl_col(N, i - 1) + 1], s.a[ci]), dn##r, y);               \
+            }                                                                                                                                \
+        }
+        LDL_ROWS(LDL_DIAGONAL)
+#undef LDL_DIAGONAL
+        const int rb0 = pl_col(N, lane) - lane, rb1 = pl_col(N, lane + 64) - (lane + 64), rb2 = pl_col(N, lane + 128) - (lane + 128);   // (i, k) at rb_k + i
+        for (int i = N - 1; i >= 0; --i) {                                     // backward: row i of L
+            const int hi = i - 1 - (s.kind[i] == PL_SECOND ? 1 : 0), ir = i >> 6;
+            const double yi = __shfl(ir == 0 ? y0 : (ir == 1 ? y1 : y2), i & 63, 64);
+#define LDL_BACKWARD(r, y, src) { if (lane + 64 * r <= hi) y = pl_axpy(y, s.a[rb##r + i], yi); }
+            LDL_ROWS(LDL_BACKWARD)
+#undef LDL_BACKWARD
+        }
+    }
+#define LDL_STORE(r, y, src)                                                                        \
+    if (src >= 0) {                                                                                 \
+        const double v = good ? y : pl_nan();                                                       \
+        if (src < POSE_NX) xt[src] = v; else xb[src - POSE_NX] = v;                                 \
+    }
+    LDL_ROWS(LDL_STORE)
+#undef LDL_STORE
+}
+#undef LDL_ROWS
+
+__global__ __launch_bounds__(LDL_WG) void hipnlp_pose_saddle_ldl_kernel(PLArgs a) {
+    __shared__ PoseLdlLds s;
+    const int tid = threadIdx.x, b = blockIdx.x, m = a.m, N = POSE_NX + m;
+    const bool with_dx = a.dx != nullptr, with_dc = a.dc != nullptr;
+    const double dx_c = (with_dx && tid < POSE_NX) ? a.dx[size_t(b) * POSE_NX + tid] : 0.0;
+    const double dc_i = (with_dc && tid >= 128 && tid - 128 < m) ? a.dc[size_t(b) * m + (tid - 128)] : 0.0;
+    double delta = 0.0;
+    int t = 0, status, pos, neg, zero;
+    for (;;) {                                                                 // the ladder: at most max_tries + 1 <= 17 turns
+        pose_ldl_assemble(s, a, b, N, tid, with_dx, dx_c, with_dc, dc_i, t > 0, delta);
+        const int st = pose_ldl_factor(s, N, tid, pos, neg, zero);
+        if (tid == 0) { s.word[0] = pos; s.word[1] = neg; s.word[2] = zero; s.word[3] = st; }
+        lds_barrier();
+        pos = s.word[0]; neg = s.word[1]; zero = s.word[2];                    // the same words in every thread: the exit is the workgroup's
+        const bool wanted = pl_inertia_wanted(pos, neg, zero, m);
+        status = pl_final_status(s.word[3], wanted, a.max_tries);
+        if (!__builtin_amdgcn_readfirstlane(int(pl_ladder_goes_on(s.word[3], wanted, t, a.max_tries)))) break;
+        ++t;
+        delta = pl_next_delta(t, delta, a.delta_init, a.kappa);
+    }
+    if (tid == 0) {
+        a.inertia[size_t(b) * 3 + 0] = pos; a.inertia[size_t(b) * 3 + 1] = neg; a.inertia[size_t(b) * 3 + 2] = zero;
+        a.status[b] = status;
+        if (a.delta) a.delta[b] = delta;
+        if (a.tries) a.tries[b] = t;
+    }
+    if (a.factor) {
+        const int nd = pl_doubles(N);
+        double* f = a.factor + size_t(b) * size_t(nd);
+        for (int e = tid; e < nd; e += LDL_WG) f[e] = s.a[e];
+        if (tid < N) a.pivots[size_t(b) * N + tid] = s.ipiv[tid];
+    }
+    const int wave = tid >> 6;
+    if (wave < a.nrhs) {
+        const size_t r = size_t(b) * size_t(a.nrhs) + size_t(wave);
+        pose_ldl_solve_wave(s, N, status == PL_OK || status == PL_EXHAUSTED, a.rhs_top + r * POSE_NX, a.rhs_bot + r * m, a.sol_top + r * POSE_NX, a.sol_bot + r * m, tid & 63);
+    }
+}
+
+// nrhs solves from a stored factor and pivot vector: no assembly, no value run.  A pivot word that names no index of the trailing
+// matrix interchanges nothing (the words are the caller's memory: nothing is addressed by them unchecked).
+__global__ __launch_bounds__(LDL_WG) void hipnlp_pose_saddle_ldl_solve_kernel(PLArgs a) {
+    __shared__ PoseLdlLds s;
+    const int tid = threadIdx.x, b = blockIdx.x, m = a.m, N = POSE_NX + m, nd = pl_doubles(N);
+    const double* f = a.factor + size_t(b) * size_t(nd);
+    if (tid < N) { s.ipiv[tid] = a.pivots[size_t(b) * N + tid]; s.perm[tid] = tid; s.kind[tid] = PL_ONE; }
+    for (int e = tid; e < nd; e += LDL_WG) s.a[e] = f[e];
+    lds_barrier();
+    if (tid == 0) {
+        int k = 0;
+        while (k < N) {
+            const int p = s.ipiv[k];
+            const bool two = p < 0 && k + 1 < N;
+            const int kk = two ? k + 1 : k;
+            int kp = (p < 0 ? -p : p) - 1;
+            if (kp < kk || kp >= N) kp = kk;
+            if (two) { s.kind[k] = PL_FIRST; s.kind[k + 1] = PL_SECOND; }
+            const int32_t u = s.perm[kk];
+            s.perm[kk] = s.perm[kp];
+            s.perm[kp] = u;
+            k = kk + 1;
+        }
+    }
+    lds_barrier();
+    const int wave = tid >> 6;
+    if (wave < a.nrhs) {
+        const size_t r = size_t(b) * size_t(a.nrhs) + size_t(wave);
+        pose_ldl_solve_wave(s, N, true, a.rhs_top + r * POSE_NX, a.rhs_bot + r * m, a.sol_top + r * POSE_NX, a.sol_bot + r * m, tid & 63);
+    }
+}
+
 thread_local std::string g_pose_create_error;
 
 }  // namespace
@@ -748,6 +1041,9 @@ struct hipnlp_pose_handle {
     PoseKktTables* d_kt = nullptr;    // tables of the KKT kernels (pose_kkt.h): a third block, the other two are what they were
     bool kkt_fits = false;            // the pattern is within what the KKT kernels stage (PoseLayout::kkt_fits)
     std::string kkt_error;
+    PoseLdlTables* d_lt = nullptr;    // table of the dense factorisation (pose_ldl.h): a fourth block
+    bool ldl_fits = false;            // the KKT matrix is within what one workgroup holds (PoseLayout::ldl_fits)
+    std::string ldl_error;
     double *d_x = nullptr, *d_pk = nullptr, *d_xr = nullptr, *d_f = nullptr, *d_grad = nullptr, *d_g = nullptr, *d_jac = nullptr, *d_cost = nullptr;
     GParams* d_gp = nullptr;
     int32_t* d_flags = nullptr;
@@ -781,7 +1077,7 @@ static void pose_free_all(hipnlp_pose_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->dev);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* dptrs[] = {h->d_tb, h->d_pt, h->d_kt, h->d_x, h->d_pk, h->d_xr, h->d_f, h->d_grad, h->d_g, h->d_jac, h->d_cost, h->d_gp, h->d_flags, h->d_sigma, h->d_lambda, h->d_hess};
+    void* dptrs[] = {h->d_tb, h->d_pt, h->d_kt, h->d_lt, h->d_x, h->d_pk, h->d_xr, h->d_f, h->d_grad, h->d_g, h->d_jac, h->d_cost, h->d_gp, h->d_flags, h->d_sigma, h->d_lambda, h->d_hess};
     for (void* q : dptrs) if (q) (void)hipFree(q);
     void* hptrs[] = {h->h_x, h->h_f, h->h_grad, h->h_g, h->h_jac, h->h_cost, h->h_flags, h->h_sigma, h->h_lambda, h->h_hess};
     for (void* q : hptrs) if (q) (void)hipHostFree(q);
@@ -914,6 +1210,16 @@ int hipnlp_pose_create(const hipnlp_pose_desc* desc, hipnlp_pose_handle** out) {
         ce = hipnlp_internal_memcpy(h->d_kt, kt, sizeof(PoseKktTables), hipMemcpyHostToDevice);
         delete kt;
         if (ce != hipSuccess) return fail(HIPNLP_E_NODEVICE, std::string("hipMemcpy KKT tables: ") + hipGetErrorString(ce));
+    }
+    h->ldl_fits = h->L.ldl_fits();
+    if (!h->ldl_fits) { h->ldl_error = h->L.error; h->L.error.clear(); }   // (not an error of the handle: the factorisation's entry points refuse)
+    else {
+        CREATE_TRY(hipMalloc(&h->d_lt, sizeof(PoseLdlTables)));
+        PoseLdlTables* lt = new PoseLdlTables();
+        h->L.fill_ldl_tables(*lt);
+        ce = hipnlp_internal_memcpy(h->d_lt, lt, sizeof(PoseLdlTables), hipMemcpyHostToDevice);
+        delete lt;
+        if (ce != hipSuccess) return fail(HIPNLP_E_NODEVICE, std::string("hipMemcpy LDL table: ") + hipGetErrorString(ce));
     }
 #undef CREATE_TRY
     *out = h;
@@ -1171,6 +1477,57 @@ int hipnlp_pose_kkt_minres_device(hipnlp_pose_handle* h, const double* hess_valu
     a.iterations = iterations_dev; a.residual = residual_dev; a.status = status_dev; a.dx = dx_dev; a.dc = dc_dev; a.minv_top = minv_top_dev; a.minv_bot = minv_bottom_dev;
     a.build_diag = build_diagonal != 0; a.floor = floor; a.rtol = rtol; a.maxit = max_iterations;
     return pose_kkt_launch(h, "hipnlp_pose_kkt_minres_device", POSE_KKT_SOLVE, a, stream);
+}
+
+// ---- the dense L D L^T of the KKT matrix per pose (pose_ldl.h): one launch each, device pointers, no workspace ------------------------------
+int hipnlp_pose_kkt_ldl_doubles(const hipnlp_pose_handle* h) {
+    if (!h) return HIPNLP_E_INVALID;
+    if (!h->ldl_fits) return HIPNLP_E_UNSUPPORTED;
+    return pl_doubles(POSE_NX + h->L.m);
+}
+
+static int pose_ldl_launch(hipnlp_pose_handle* h, const char* who, bool factor, PLArgs& a, void* stream) {
+    if (!h->ldl_fits) { h->err = std::string(who) + ": " + h->ldl_error; return HIPNLP_E_UNSUPPORTED; }
+    HIP_TRY(h, hipSetDevice(h->dev));
+    a.lt = h->d_lt;
+    a.m = h->L.m; a.nnz = h->L.nnz; a.hnnz = h->L.hnnz;
+    hipStream_t s = stream ? hipStream_t(stream) : h->stream;
+    const dim3 grid(unsigned(h->batch)), block(LDL_WG);
+    if (factor) hipLaunchKernelGGL(hipnlp_pose_saddle_ldl_kernel, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(hipnlp_pose_saddle_ldl_solve_kernel, grid, block, 0, s, a);
+    HIP_TRY(h, hipGetLastError());
+    return HIPNLP_OK;
+}
+
+int hipnlp_pose_kkt_ldl_device(hipnlp_pose_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev, const double* dc_dev, int nrhs,
+                               const double* rhs_top_dev, const double* rhs_bottom_dev, double* sol_top_dev, double* sol_bottom_dev, int32_t* inertia_dev, int32_t* status_dev,
+                               double* delta_dev, int32_t* tries_dev, double delta_init, double kappa, int max_tries, double* factor_dev, int32_t* pivots_dev, void* stream) {
+    if (!h) return HIPNLP_E_INVALID;
+    if (const char* e = pl_factor_call_error(hess_values_dev, jac_values_dev, nrhs, rhs_top_dev, rhs_bottom_dev, sol_top_dev, sol_bottom_dev, inertia_dev, status_dev, delta_init,
+                                             kappa, max_tries, factor_dev, pivots_dev)) {
+        h->err = std::string("hipnlp_pose_kkt_ldl_device: ") + e;
+        return HIPNLP_E_INVALID;
+    }
+    PLArgs a{};
+    a.hess = hess_values_dev; a.jac = jac_values_dev; a.dx = dx_dev; a.dc = dc_dev; a.nrhs = nrhs;
+    a.rhs_top = rhs_top_dev; a.rhs_bot = rhs_bottom_dev; a.sol_top = sol_top_dev; a.sol_bot = sol_bottom_dev;
+    a.inertia = inertia_dev; a.status = status_dev; a.delta = delta_dev; a.tries = tries_dev;
+    a.delta_init = max_tries > 0 ? delta_init : 0.0; a.kappa = max_tries > 0 ? kappa : 0.0; a.max_tries = max_tries;
+    a.factor = factor_dev; a.pivots = pivots_dev;
+    return pose_ldl_launch(h, "hipnlp_pose_kkt_ldl_device", true, a, stream);
+}
+
+int hipnlp_pose_kkt_ldl_solve_device(hipnlp_pose_handle* h, const double* factor_dev, const int32_t* pivots_dev, int nrhs, const double* rhs_top_dev,
+                                     const double* rhs_bottom_dev, double* sol_top_dev, double* sol_bottom_dev, void* stream) {
+    if (!h) return HIPNLP_E_INVALID;
+    if (const char* e = pl_solve_call_error(factor_dev, pivots_dev, nrhs, rhs_top_dev, rhs_bottom_dev, sol_top_dev, sol_bottom_dev)) {
+        h->err = std::string("hipnlp_pose_kkt_ldl_solve_device: ") + e;
+        return HIPNLP_E_INVALID;
+    }
+    PLArgs a{};
+    a.factor = const_cast<double*>(factor_dev); a.pivots = const_cast<int32_t*>(pivots_dev); a.nrhs = nrhs;       // (sources here: the solve kernel stores to neither)
+    a.rhs_top = rhs_top_dev; a.rhs_bot = rhs_bottom_dev; a.sol_top = sol_top_dev; a.sol_bot = sol_bottom_dev;
+    return pose_ldl_launch(h, "hipnlp_pose_kkt_ldl_solve_device", false, a, stream);
 }
 
 int hipnlp_pose_cost_terms(hipnlp_pose_handle* h, double* values) {

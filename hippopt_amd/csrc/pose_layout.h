@@ -6,6 +6,7 @@
 #include "layout.h"
 #include "pose_hess_body.h"
 #include "pose_kkt.h"
+#include "pose_ldl.h"
 #include "pose_products.h"
 
 namespace hipnlp {
@@ -252,6 +253,25 @@ struct PoseLayout {
         for (int q = 0; q < nnz; ++q) { const int e = jrowent[size_t(q)]; t.row_word[q] = pp_word(e, jcol[size_t(e)]); }
         for (size_t q = 0; q < htouch.size(); ++q) t.touch_word[q] = pp_word(htouch[q].pos, htouch[q].other);
         for (int c = 0; c < PK_WG; ++c) t.hdiag[c] = c < POSE_NX ? hdiag[size_t(c)] : -1;
+    }
+
+    // the dense factorisation (pose_ldl.h) holds the packed lower triangle of the KKT matrix, order 81 + m, in one workgroup's LDS and
+    // assembles it from both value runs: the caps of kkt_fits and an order of at most PL_MAX_N.  A pattern beyond them is refused by the
+    // entry points (HIPNLP_E_UNSUPPORTED), never truncated.
+    bool ldl_fits() {
+        if (!kkt_fits()) return false;
+        if (n + m > PL_MAX_N) {
+            error = "the KKT matrix of the pose has order " + std::to_string(n + m) + ": more than the dense factorisation holds (" + std::to_string(PL_MAX_N) + ")";
+            return false;
+        }
+        return true;
+    }
+
+    // the device table of the assembly: row and column of every stored entry as its place in the packed lower triangle of order 81 + m
+    void fill_ldl_tables(PoseLdlTables& t) const {
+        const int N = n + m;
+        for (int e = 0; e < PK_HESS_CAP; ++e) t.hess_at[e] = e < hnnz ? pl_at(N, hrow[size_t(e)], hcol[size_t(e)]) : -1;
+        for (int e = 0; e < PP_ENT_CAP; ++e) t.jac_at[e] = e < nnz ? pl_at(N, n + irow[size_t(e)], jcol[size_t(e)]) : -1;
     }
 
     // canonical bounds (CasADi Opti canon form) of one pose from its parameter vector

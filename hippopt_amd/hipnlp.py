@@ -39,6 +39,7 @@ EXPORTS = [
     "hipnlp_pose_hess_nnz", "hipnlp_pose_hess_sparsity", "hipnlp_pose_eval_hess", "hipnlp_pose_eval_hess_device",
     "hipnlp_pose_eval_lagrangian_grad_device", "hipnlp_pose_eval_jac_vec_device", "hipnlp_pose_eval_hess_vec_device",
     "hipnlp_pose_kkt_times_device", "hipnlp_pose_kkt_diag_precond_device", "hipnlp_pose_kkt_minres_device",
+    "hipnlp_pose_kkt_ldl_doubles", "hipnlp_pose_kkt_ldl_device", "hipnlp_pose_kkt_ldl_solve_device",
     # include/hipnlp_ipopt.h: IPOPT's C callback quartet (+ eval_h) on top of the functions above
     "hipnlp_ipopt_eval_f", "hipnlp_ipopt_eval_grad_f", "hipnlp_ipopt_eval_g", "hipnlp_ipopt_eval_jac_g", "hipnlp_ipopt_eval_h",
     "hipnlp_ipopt_sizes", "hipnlp_ipopt_bounds", "hipnlp_ipopt_attach", "hipnlp_ipopt_detach", "hipnlp_ipopt_set_early_outputs",
@@ -183,6 +184,10 @@ def load_library(path=None):
         lib.hipnlp_pose_kkt_times_device.argtypes = [vp] * 10
         lib.hipnlp_pose_kkt_diag_precond_device.argtypes = [vp] * 7 + [C.c_double, vp]
         lib.hipnlp_pose_kkt_minres_device.argtypes = [vp] * 14 + [C.c_int, C.c_double, C.c_double, C.c_int, vp]
+    if hasattr(lib, "hipnlp_pose_kkt_ldl_device"):
+        lib.hipnlp_pose_kkt_ldl_doubles.argtypes = [vp]
+        lib.hipnlp_pose_kkt_ldl_device.argtypes = [vp] * 5 + [C.c_int] + [vp] * 8 + [C.c_double, C.c_double, C.c_int] + [vp] * 3
+        lib.hipnlp_pose_kkt_ldl_solve_device.argtypes = [vp] * 3 + [C.c_int] + [vp] * 5
     lib.hipnlp_hess_nnz.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.hipnlp_hess_sparsity.argtypes = [vp, ip, ip]
     lib.hipnlp_eval_hess.argtypes = [vp, dp, dp, dp, dp]
@@ -856,6 +861,37 @@ class HipPose:
                                                            vp(sol_top_ptr or None), vp(sol_bottom_ptr or None), vp(iterations_ptr or None), vp(residual_ptr or None),
                                                            vp(status_ptr or None), vp(dx_ptr or None), vp(dc_ptr or None), vp(minv_top_ptr or None), vp(minv_bottom_ptr or None),
                                                            1 if build_diagonal else 0, float(floor), float(rtol), int(max_iterations), vp(stream or None)))
+
+    # ---- the dense L D L^T of the KKT matrix per pose (pose_ldl.h): one launch each, one workgroup per pose, no workspace ----------------------
+    def kkt_ldl_doubles(self):
+        """N (N + 1) / 2, N = 81 + m: the doubles of one pose's packed factor (hipnlp_pose_kkt_ldl_doubles)"""
+        n = self.lib.hipnlp_pose_kkt_ldl_doubles(self.h)
+        if n < 0:
+            raise HipNlpError(n, "hipnlp_pose_kkt_ldl_doubles: the KKT matrix of this handle is beyond what the dense factorisation holds")
+        return n
+
+    def kkt_ldl_device(self, hess_values_ptr, jac_values_ptr, inertia_ptr, status_ptr, dx_ptr=0, dc_ptr=0, nrhs=0, rhs_top_ptr=0, rhs_bottom_ptr=0, sol_top_ptr=0,
+                       sol_bottom_ptr=0, delta_ptr=0, tries_ptr=0, delta_init=0.0, kappa=0.0, max_tries=0, factor_ptr=0, pivots_ptr=0, stream=None):
+        """Assemble K = [[H + diag dx + delta I, J^T], [J, -diag dc]] of every pose from the two value runs, factor it (Bunch-Kaufman
+        L D L^T, packed, in the workgroup's LDS), count the inertia, climb the regularisation ladder and solve nrhs (0 .. 8) right-hand
+        sides [batch][nrhs][81] / [batch][nrhs][m], all in ONE launch (hipnlp_pose_kkt_ldl_device).  inertia [batch][3] int32 (+, -, 0);
+        status [batch] int32: 0 factored, 1 exactly singular, 2 data not finite, 3 ladder exhausted; delta [batch] and tries [batch] int32
+        of the last try (optional).  max_tries = 0: factor once, report the inertia as it is; else try t >= 1 adds delta_init kappa^(t-1)
+        to the top block's diagonal until the inertia is (81, m, 0) or t = max_tries (<= 16).  factor [batch][kkt_ldl_doubles()] and
+        pivots [batch][81 + m] int32 (both or neither) receive the factor for kkt_ldl_solve_device.  No workspace: calls on different
+        streams are independent."""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_pose_kkt_ldl_device(self.h, vp(hess_values_ptr or None), vp(jac_values_ptr or None), vp(dx_ptr or None), vp(dc_ptr or None), int(nrhs),
+                                                        vp(rhs_top_ptr or None), vp(rhs_bottom_ptr or None), vp(sol_top_ptr or None), vp(sol_bottom_ptr or None),
+                                                        vp(inertia_ptr or None), vp(status_ptr or None), vp(delta_ptr or None), vp(tries_ptr or None), float(delta_init),
+                                                        float(kappa), int(max_tries), vp(factor_ptr or None), vp(pivots_ptr or None), vp(stream or None)))
+
+    def kkt_ldl_solve_device(self, factor_ptr, pivots_ptr, nrhs, rhs_top_ptr, rhs_bottom_ptr, sol_top_ptr, sol_bottom_ptr, stream=None):
+        """nrhs (1 .. 8) solves from the factor and pivots kkt_ldl_device stored, in ONE launch (hipnlp_pose_kkt_ldl_solve_device): no
+        assembly, no value run; the bits of the solves of the call that stored them"""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_pose_kkt_ldl_solve_device(self.h, vp(factor_ptr or None), vp(pivots_ptr or None), int(nrhs), vp(rhs_top_ptr or None),
+                                                              vp(rhs_bottom_ptr or None), vp(sol_top_ptr or None), vp(sol_bottom_ptr or None), vp(stream or None)))
 
     def cost_terms(self):
         names = [self.lib.hipnlp_pose_cost_term_name(i).decode() for i in range(_abi.POSE_NCOST_TERMS)]

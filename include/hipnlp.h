@@ -910,6 +910,45 @@ int hipnlp_pose_kkt_minres_device(hipnlp_pose_handle* h, const double* hess_valu
                                   const double* rhs_bottom_dev, double* sol_top_dev, double* sol_bottom_dev, int32_t* iterations_dev, double* residual_dev,
                                   int32_t* status_dev, const double* dx_dev /*or NULL*/, const double* dc_dev /*or NULL*/, const double* minv_top_dev /*or NULL*/,
                                   const double* minv_bottom_dev /*or NULL*/, int build_diagonal, double floor, double rtol, int max_iterations, void* stream);
+
+/* The dense L D L^T factorisation of the same K = [[H + diag d_x + delta I, J^T], [J, -diag d_c]] per pose, with its INERTIA, a
+ * regularisation ladder and the solves — what an interior-point step needs and MINRES cannot give.  The order N = 81 + m is at most 176:
+ * one workgroup holds the packed lower triangle (N (N + 1) / 2 doubles) in its LDS, assembles it from the two stored value runs, factors
+ * it by Bunch-Kaufman partial pivoting (the algorithm of LAPACK's unblocked DSPTF2('L'): 1x1 and 2x2 pivots, alpha = (1 + sqrt 17) / 8),
+ * reads the inertia off D and solves.  Each call is ONE launch on a grid of `batch` workgroups of 1 024 threads, enqueued on `stream`
+ * (NULL: the handle's own), not synchronised; no workspace, nothing owned by the handle: calls on different streams are independent.
+ * Every element of the factor and of a solution is one fixed chain of fused multiply-adds (hippopt_amd/csrc/pose_ldl.h): the same bits on
+ * every launch, at every batch position.
+ *   hipnlp_pose_kkt_ldl_doubles       N (N + 1) / 2, the doubles of one pose's packed factor
+ *   hipnlp_pose_kkt_ldl_device        assemble, factor, count, climb the ladder, then nrhs solves (0 <= nrhs <= 8; right-hand sides
+ *                                     [batch][nrhs][81] and [batch][nrhs][m], solutions alike; all four NULL with nrhs == 0).
+ *                                     inertia_dev [batch][3] int32: positive, negative, zero eigenvalues.  status_dev [batch] int32:
+ *                                     0 factored (and, with a ladder, the inertia is (81, m, 0)); 1 exactly singular: a pivot column of
+ *                                     zeros, counted as ONE zero, the factorisation ends there; 2 data that is not finite; 3 the ladder
+ *                                     is exhausted.  The ladder (IPOPT's inertia correction, top block only): try 0 has delta = 0, try
+ *                                     t >= 1 has delta_1 = delta_init, delta_(t+1) = delta_t * kappa added to the 81 diagonal elements of
+ *                                     the top block on a re-assembly; it ends at the first try with inertia (81, m, 0), at status 2, or
+ *                                     at try max_tries (<= 16); max_tries == 0: factor once, report the inertia as it is.  Status,
+ *                                     inertia, factor and solutions are those of the last try; delta_dev [batch] its delta and tries_dev
+ *                                     [batch] int32 its number (either may be NULL).  With status 1 or 2 the solutions are NaN.
+ *                                     factor_dev [batch][doubles] and pivots_dev [batch][N] int32 (both or neither) receive the factor:
+ *                                     D and the multipliers in the packed lower triangle, the pivot vector in LAPACK's convention
+ *                                     (1-based; k > 0: a 1x1 pivot; a pair of -k: a 2x2 pivot) — the values of DSPTF2, but EVERY
+ *                                     interchange is applied to whole rows of L (P K P^T = L D L^T), which DSPTRS would not expect.
+ *   hipnlp_pose_kkt_ldl_solve_device  nrhs (1 .. 8) solves from a stored factor and pivot vector: no assembly, no value run read; the
+ *                                     bits of the solves of the call that stored them.
+ * HIPNLP_E_INVALID: a null handle or required pointer, nrhs out of range, one of factor_dev / pivots_dev alone, max_tries outside
+ * 0 .. 16, and with max_tries > 0 a delta_init that is not a finite number > 0 or a kappa that is not a finite number > 1.
+ * HIPNLP_E_UNSUPPORTED: the handle's pattern is beyond hipnlp_pose_kkt_times_device's caps or 81 + m > 176.  Measured:
+ * profiles/r15_pose_ldl.txt (tools/pose_ldl_probe.py) — 0.24 x torch.linalg.solve on the dense K, slower than MINRES at dx, dc in U[1, 2]. */
+int hipnlp_pose_kkt_ldl_doubles(const hipnlp_pose_handle* h);
+int hipnlp_pose_kkt_ldl_device(hipnlp_pose_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev /*or NULL*/,
+                               const double* dc_dev /*or NULL*/, int nrhs, const double* rhs_top_dev, const double* rhs_bottom_dev, double* sol_top_dev,
+                               double* sol_bottom_dev, int32_t* inertia_dev /*[batch][3]*/, int32_t* status_dev /*[batch]*/, double* delta_dev /*or NULL*/,
+                               int32_t* tries_dev /*or NULL*/, double delta_init, double kappa, int max_tries, double* factor_dev /*or NULL*/,
+                               int32_t* pivots_dev /*or NULL*/, void* stream);
+int hipnlp_pose_kkt_ldl_solve_device(hipnlp_pose_handle* h, const double* factor_dev, const int32_t* pivots_dev, int nrhs, const double* rhs_top_dev,
+                                     const double* rhs_bottom_dev, double* sol_top_dev, double* sol_bottom_dev, void* stream);
 int hipnlp_pose_cost_terms(hipnlp_pose_handle* h, double* values /*[batch][HIPNLP_POSE_NCOST_TERMS]*/);
 const char* hipnlp_pose_cost_term_name(int i);
 int hipnlp_pose_num_row_blocks(const hipnlp_pose_handle* h);
