@@ -41,6 +41,7 @@
 #include "knot_stage.h"
 #include "knot_values_stage.h"
 #include "layout.h"
+#include "multi_pool.h"
 
 using namespace hipnlp;
 typedef unsigned long long u64;
@@ -2883,53 +2884,15 @@ struct MultiState {
     std::vector<double*> hd_cost;         // ... and its device-visible address
     std::vector<size_t> cost_off;
     std::vector<double> shard_us;         // [shards][2] of the last evaluation: enqueue, completion seen (host clock, from the start of the enqueue loop)
-    // ---- one launching thread per shard (hipnlp_multi_set_threads) -------------------------------------------------------------------
-    // Enqueueing a kernel costs the host 4 - 6 us and waiting for a stream a few more: done by the caller's thread one shard after the
-    // other, the last of eight shards would start 40 us after the first — longer than the whole callback of one device.  With threads on,
-    // shard i > 0 has a worker bound to its device: the caller publishes a job (a ticket number), runs shard 0's part itself and waits
-    // for the others; every worker stages / launches / waits for ITS shard.  A worker polls for the next ticket for `spin_us` after its
-    // last job (IPOPT's callbacks come in bursts, microseconds apart) and sleeps on a condition variable after that (between bursts
-    // IPOPT factorises for milliseconds: no core is burnt meanwhile; the first callback of a burst pays one wake-up).
-    std::vector<std::thread> workers;
-    std::function<int(size_t)> job;       // what every shard does for the ticket in flight; rc per shard in job_rc
-    std::vector<int> job_rc;
-    std::atomic<unsigned long long> ticket{0};
-    std::atomic<int> done{0};
-    std::atomic<int> sleepers{0};
-    std::atomic<bool> quit{false};
-    std::mutex mx;
-    std::condition_variable cv;
-    double spin_us = 200.0;
-    bool threads = false;
+    MultiPool pool;                       // one launching thread per shard (hipnlp_multi_set_threads): multi_pool.h
 };
 
-static void multi_worker(MultiState* M, size_t i) {
-    (void)hipSetDevice(M->shards[i]->dev);   // (the current device is a property of the thread: set once)
-    unsigned long long seen = 0;
-    auto last = std::chrono::steady_clock::now();
-    for (;;) {
-        unsigned long long t = M->ticket.load(std::memory_order_acquire);
-        if (t == seen) {
-            if (M->quit.load(std::memory_order_relaxed)) return;
-            if (std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - last).count() < M->spin_us) { __builtin_ia32_pause(); continue; }
-            std::unique_lock<std::mutex> lock(M->mx);
-            M->sleepers.fetch_add(1, std::memory_order_seq_cst);
-            M->cv.wait(lock, [&] { return M->ticket.load(std::memory_order_acquire) != seen || M->quit.load(std::memory_order_relaxed); });
-            M->sleepers.fetch_sub(1, std::memory_order_seq_cst);
-            continue;
-        }
-        seen = t;
-        M->job_rc[i] = M->job(i);
-        M->done.fetch_add(1, std::memory_order_release);
-        last = std::chrono::steady_clock::now();
-    }
-}
 // every shard runs job(i): by its worker (threads on), shard 0 by the caller; or one after the other by the caller.  First failure wins.
 static int multi_failed(hipnlp_handle* h, size_t i, int rc);
 static int multi_run(hipnlp_handle* h, std::function<int(size_t)> job) {
     MultiState& M = *h->multi;
     const size_t S = M.shards.size();
-    if (!M.threads || S == 1) {
+    if (!M.pool.threads || S == 1) {
         for (size_t i = 0; i < S; ++i) {
             HIP_TRY(h, hipSetDevice(M.shards[i]->dev));
             const int rc = job(i);
@@ -2937,32 +2900,15 @@ static int multi_run(hipnlp_handle* h, std::function<int(size_t)> job) {
         }
         return HIPNLP_OK;
     }
-    M.job = std::move(job);
-    M.done.store(0, std::memory_order_relaxed);
-    M.ticket.fetch_add(1, std::memory_order_seq_cst);
-    if (M.sleepers.load(std::memory_order_seq_cst) > 0) { std::lock_guard<std::mutex> lock(M.mx); M.cv.notify_all(); }
-    M.job_rc[0] = M.job(0);
-    while (M.done.load(std::memory_order_acquire) < int(S) - 1) __builtin_ia32_pause();
-    for (size_t i = 0; i < S; ++i) if (M.job_rc[i] != HIPNLP_OK) return multi_failed(h, i, M.job_rc[i]);
-    return HIPNLP_OK;
-}
-static void multi_stop_workers(MultiState* M) {
-    if (M->workers.empty()) return;
-    {
-        std::lock_guard<std::mutex> lock(M->mx);
-        M->quit.store(true, std::memory_order_seq_cst);
-    }
-    M->cv.notify_all();
-    for (std::thread& t : M->workers) t.join();
-    M->workers.clear();
-    M->quit.store(false, std::memory_order_seq_cst);
-    M->threads = false;
+    size_t failed = 0;
+    const int rc = M.pool.run(std::move(job), &failed);
+    return rc != HIPNLP_OK ? multi_failed(h, failed, rc) : HIPNLP_OK;
 }
 
 static void multi_destroy(hipnlp_handle* h) {
     MultiState* M = h->multi;
     if (!M) return;
-    multi_stop_workers(M);
+    M->pool.stop();
     for (hipnlp_handle* s : M->shards) hipnlp_destroy(s);
     if (M->h_cost) (void)hipHostFree(M->h_cost);
     delete M;
@@ -3090,7 +3036,7 @@ static int multi_evaluate(hipnlp_handle* h, double* const o[3], bool vary_only, 
         return HIPNLP_OK;
     };
     int rc;
-    if (M.threads && M.shards.size() > 1) {
+    if (M.pool.threads && M.shards.size() > 1) {
         rc = multi_run(h, [&](size_t i) -> int { const int r = enqueue(i); return r != HIPNLP_OK ? r : wait(i); });
         if (t_enqueued) *t_enqueued = t0 + std::chrono::duration_cast<std::chrono::steady_clock::duration>(std::chrono::duration<double, std::micro>(M.shard_us[0]));
     } else {   // the caller's thread: every launch first, then every wait
@@ -3122,7 +3068,7 @@ static int multi_fetch(hipnlp_handle* h, int q, double* dst, double* dst_dev, bo
                                int64_t(L.nnz), L.nnz_v[VAR_FIRST], L.nnz_v[VAR_INTERIOR], L.nvary_v[VAR_FIRST], L.nvary_v[VAR_INTERIOR], L.nvary_v[VAR_LAST]);
             HIP_TRY(s, hipGetLastError());
         } else HIP_TRY(s, copy_rows(dst, s->d_jac, size_t(L.nnz), size_t(s->dims.shard_jac_off), size_t(s->dims.shard_nnz), B, hipMemcpyDeviceToHost, s->stream));
-        if (h->multi->threads) HIP_TRY(s, hipStreamSynchronize(s->stream));   // (its own thread waits for it; the caller's multi_sync then finds the streams idle)
+        if (h->multi->pool.threads) HIP_TRY(s, hipStreamSynchronize(s->stream));   // (its own thread waits for it; the caller's multi_sync then finds the streams idle)
         return HIPNLP_OK;
     });
 }
@@ -3185,8 +3131,8 @@ int hipnlp_multi_create(const hipnlp_desc* desc, const int32_t* devices, int n_d
     (void)hipSetDevice(h->dev);
     *out = h;
     // one launching thread per shard by default: from the caller's thread alone the waits for the shards' streams come one after the other,
-    // ~9 us each (measured with shards of one card: 47 / 64 / 114 us per 100-knot callback with 2 / 4 / 8 shards against 45 / 56 / 72 with
-    // threads, profiles/r06_multi_probe.txt); hipnlp_multi_set_threads(h, 0, -1) turns them off
+    // ~9 us each (measured with shards of one card: 47 / 62 / 115 us per 100-knot callback with 2 / 4 / 8 shards against 45 / 55 / 71 with
+    // threads, profiles/r16_multi_pool.txt); hipnlp_multi_set_threads(h, 0, -1) turns them off
     if (n_devices > 1 && hipnlp_multi_set_threads(h, 1, -1.0) != HIPNLP_OK) h->err.clear();   // (no threads: the caller's thread does it all)
     return HIPNLP_OK;
 }
@@ -3208,18 +3154,12 @@ int hipnlp_multi_info(const hipnlp_handle* h, int32_t* n_shards, int32_t* device
 int hipnlp_multi_set_threads(hipnlp_handle* h, int on, double spin_us) {
     if (!h || !h->multi) return HIPNLP_E_INVALID;
     MultiState* M = h->multi;
-    if (spin_us >= 0.0) M->spin_us = spin_us;
-    if (!on) { multi_stop_workers(M); return HIPNLP_OK; }
-    if (M->threads) return HIPNLP_OK;
-    M->job_rc.assign(M->shards.size(), HIPNLP_OK);
-    try {
-        for (size_t i = 1; i < M->shards.size(); ++i) M->workers.emplace_back(multi_worker, M, i);
-    } catch (...) {
-        multi_stop_workers(M);
+    if (spin_us >= 0.0) M->pool.spin_us = spin_us;
+    if (!on) { M->pool.stop(); return HIPNLP_OK; }
+    if (!M->pool.start(M->shards.size(), [M](size_t i) { (void)hipSetDevice(M->shards[i]->dev); })) {   // (the current device is a property of the thread)
         h->err = "hipnlp_multi_set_threads: could not start the launching threads";
         return HIPNLP_E_ALLOC;
     }
-    M->threads = true;
     return HIPNLP_OK;
 }
 int hipnlp_multi_breakdown(const hipnlp_handle* h, double* us) {
@@ -3739,12 +3679,12 @@ int hipnlp_eval_hess_at(hipnlp_handle* h, const double* x, int new_x, const doub
             s->early_store = h->early_store;
             const int rl = hess_launch(s, xs, sl, sl + B, dest, s->stream, true, early_run, int64_t(hn));
             if (rl != HIPNLP_OK) return rl;
-            if (!h->multi->threads) return HIPNLP_OK;   // (the caller's thread: every launch first, the waits below)
+            if (!h->multi->pool.threads) return HIPNLP_OK;   // (the caller's thread: every launch first, the waits below)
             HIP_TRY(s, hipStreamSynchronize(s->stream));
             return HIPNLP_OK;
         });
         if (rm != HIPNLP_OK) return rm;
-        return h->multi->threads ? HIPNLP_OK : multi_sync(h);
+        return h->multi->pool.threads ? HIPNLP_OK : multi_sync(h);
     };
     // the values leave the kernel as PCIe stores into the pinned block — or straight into the CALLER'S array when that lies in a
     // registered range (no 1.2 MB host copy behind the launch): registered by the caller, or by the handle itself at the array's second

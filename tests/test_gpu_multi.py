@@ -187,3 +187,124 @@ def test_solver_on_two_shards_walks_the_single_device_iterates(model):
         assert it_1 == it_2 and np.array_equal(x_1, x_2) and f_1 == f_2 and pr_1 == pr_2
     assert info_1["callbacks"] == info_2["callbacks"] and out_1.cost_value == out_2.cost_value
     assert out_1.cost_values == out_2.cost_values
+
+
+class step_limit:
+    """a time limit of its own for one step of a lifecycle test: a caller left waiting for a worker that was never woken would wait
+    for ever (there is no number to bound a kernel's length by inside the library) — here the process is ended instead, with the
+    tracebacks of all threads.  The steps take milliseconds, creating a handle a few seconds: the limit only has to be finite."""
+
+    def __init__(self, seconds=60.0):
+        self.seconds = seconds
+
+    def __enter__(self):
+        import faulthandler
+        import sys
+        faulthandler.dump_traceback_later(self.seconds, exit=True, file=sys.__stderr__)
+
+    def __exit__(self, *exc):
+        import faulthandler
+        faulthandler.cancel_dump_traceback_later()
+        return False
+
+
+@pytest.mark.parametrize("n_shards", [2, 4])
+def test_launching_threads_lifecycle_keeps_the_plain_handles_bits(model, HipNlp, n_shards):
+    """hipnlp_multi_set_threads through every transition of the pool's life (multi_pool.h; the pool itself: tests/test_multi_pool.py on
+    the CPU): on as created, off, on again — the workers of the second start must not take the ticket of an evaluation before the stop
+    for a new one, whose job captured a frame that has returned —, asleep, a repeated `on`, spin_us changed under running workers,
+    more restarts, two handles interleaved, one closed while the other works, closed with the workers asleep.  After every step f,
+    grad f, g, jac g, the cost terms and the Hessian values of three iterates are the plain handle's bits, and the front has counted
+    exactly the evaluations that were asked for."""
+    import time
+    st = periodic_step_settings(12, model)
+    x, p = make_workload(st, model, batch=1, seed=7500)
+    kw = dict(detect_simple_bounds=True, jac_varying_first=True)
+    with step_limit():
+        plain, multi = HipNlp(st, model, **kw), HipNlp(st, model, devices=[0] * n_shards, **kw)
+        for e in (plain, multi):
+            e.set_params(p)
+    assert len(multi.shards()) == n_shards and same_kernel(12, 1, multi.shards())
+    lam = np.random.RandomState(12).standard_normal((1, plain.m))
+    xs = iterates(x, 3, seed=9)
+    with step_limit():
+        ref = [(plain.eval(xi), plain.cost_terms()[1].copy(), plain.eval_hess(xi, 0.7, lam)) for xi in xs]   # computed once, compared with after every step
+
+    def arrays(e):
+        return (np.empty(1), np.empty((1, e.n)), np.empty((1, e.m)), np.empty((1, e.nnz))), np.empty((1, e.hess_nnz()))
+
+    def check(step, handles):
+        """every handle of `handles` (handle, out, hess) evaluates the three iterates, interleaved with the others"""
+        with step_limit():
+            before = [e.host_stats()["evaluations"] for e, _, _ in handles]
+            for i, (xi, (r_eval, r_terms, r_hess)) in enumerate(zip(xs, ref)):
+                for e, out, hess in handles:
+                    got = e.eval(xi, out=out)                    # (the same arrays every call: registered at their second sight)
+                    for name, u, v in zip(("f", "grad", "g", "jac"), got, r_eval):
+                        assert bits_equal(u, v), (step, name, i)
+                    assert bits_equal(e.cost_terms()[1], r_terms), (step, i)
+                    assert bits_equal(e.eval_hess(xi, 0.7, lam, out=hess), r_hess), (step, i)
+            for (e, _, _), b in zip(handles, before):
+                assert e.host_stats()["evaluations"] == b + len(xs), step   # (a job run once more would be launches nobody asked for)
+
+    first = (multi,) + arrays(multi)
+    check("1: as created, threads on", [first])
+    multi.set_threads(False)
+    check("2: off", [first])
+    multi.set_threads(True)
+    check("3: off -> on", [first])
+    time.sleep(0.01)                                            # (the workers go to sleep: the next call wakes them)
+    check("4: woken", [first])
+    multi.set_threads(True)
+    check("5: on again", [first])
+    multi.set_threads(True, spin_us=0.0)
+    check("6: spin_us = 0 under running workers", [first])
+    for again in range(2):
+        multi.set_threads(False)
+        multi.set_threads(True)
+        check("7: off -> on, %d" % again, [first])
+    with step_limit():
+        multi_2 = HipNlp(st, model, devices=[0] * n_shards, **kw)
+        multi_2.set_params(p)
+    second = (multi_2,) + arrays(multi_2)
+    check("8: two handles", [first, second])
+    check("8: two handles, the other first", [second, first])
+    with step_limit():
+        multi.close()
+    check("8: the first closed", [second])
+    time.sleep(0.01)
+    with step_limit():
+        multi_2.close()                                         # 9: closed with threads on and the workers asleep
+        plain.close()
+
+
+def test_solver_on_two_shards_walks_the_same_iterates_after_threads_off_and_on(model):
+    """HipNlpSolver(devices=[0, 0]) solved twice from one guess with its engine's launching threads turned off and on in between: the
+    second solve's workers are new ones, and it walks the first solve's iterates"""
+    from hippopt_amd.turnkey_planners.humanoid_kinodynamic import Planner, Settings
+    numeric = single_step_settings(30, model)
+    st = Settings.from_numeric(numeric, solver_options={"max_iter": 3})
+    pl = Planner(st, model, error_on_fail=False, inner_solver="trust-constr", devices=[0, 0])
+    sol = pl.optimization_solver
+    x, p = make_workload(st, model, batch=1, seed=61)
+    guess = pl.get_initial_guess()
+    guess.from_dict({n: x[0][off:off + size].reshape(shape) for n, (off, size, shape) in sol._var_index.items()})
+    guess.from_dict({n: p[0][off:off + size].reshape(shape) for n, (off, size, shape) in sol._par_index.items()})
+    sol.set_initial_guess(guess)
+    runs = []
+    for toggled in (False, True):
+        if toggled:
+            eng = sol.engine()
+            assert len(eng.shards()) == 2
+            eng.set_threads(False)
+            eng.set_threads(True)
+        sol.iterate_trace = []
+        with step_limit(300.0):                                 # (the stand-in driver factorises on the CPU: a second or two per iteration)
+            out = pl.solve()
+        runs.append((out, sol.iterate_trace, sol._last_info))
+    (out_1, trace_1, info_1), (out_2, trace_2, info_2) = runs
+    assert len(trace_1) == len(trace_2) >= 3
+    for (it_1, x_1, f_1, pr_1), (it_2, x_2, f_2, pr_2) in zip(trace_1, trace_2):
+        assert it_1 == it_2 and np.array_equal(x_1, x_2) and f_1 == f_2 and pr_1 == pr_2
+    assert info_1["callbacks"] == info_2["callbacks"] and out_1.cost_value == out_2.cost_value
+    assert out_1.cost_values == out_2.cost_values

@@ -44,8 +44,8 @@ def main():
     for shards, threads in [(0, False), (1, False), (2, False), (2, True), (4, False), (4, True), (8, False), (8, True)]:
         eng = HipNlp(st, model, detect_simple_bounds=True, jac_varying_first=True, devices=None if shards == 0 else [0] * shards)
         eng.set_params(p)
-        if threads:
-            eng.set_threads(True)
+        if shards:
+            eng.set_threads(threads)   # (creation turns them on for more than one shard: a `threads: false` row has to turn them off)
         out = (np.empty(1), np.empty((1, eng.n)), np.empty((1, eng.m)), np.empty((1, eng.nnz)))
         row = {"shards": shards, "threads": threads}
         row["all_us"] = round(timed(eng, xs, out, calls), 2)
