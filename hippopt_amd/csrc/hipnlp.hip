@@ -1834,6 +1834,404 @@ void hipnlp_saddle_diag_kernel(SaddleDiagArgs a) {
 }
 
 
+// =====================================================================================================================
+// The block top of a preconditioner for that solve (hipnlp_kkt_block_factor_device, hipnlp_kkt_block_apply_device,
+// hipnlp_kkt_minres_block_device; knot_ldl.h has every expression and every order): a dense L |D| L^T per knot block of H + diag d_x.
+//   factor  ONE workgroup per (knot, trajectory) holds the packed lower triangle of order 189 (143 640 B) and 5 392 B more in static LDS —
+//           one workgroup per CU — assembles it from the stored Hessian run, factors it as hipnlp_pose_saddle_ldl_kernel does (1 024
+//           threads: every wave searches the column itself, thread t owns the pair of index t in an interchange and the multipliers of
+//           row k + kstep + t, the trailing update has the columns dealt to the waves and the lanes along the packed column; four
+//           barriers per pivot step), then forms e / o and stores the factor, the pivot words, e, o, the inertia and the status.
+//           Nothing leaves the CU before the stores, no workgroup waits for another, no atomics, every loop is bounded by 189.
+//   apply   ONE wave per knot: the vector in three registers per lane, y_k by a lane read, the columns (forward) and rows (backward)
+//           of L streamed from the stored factor with the next KLA_AHEAD of them already requested — no address depends on data.
+//           The backward pass reads a row of L: a stride that grows lane by lane (the factor is stored once, by columns).
+// Every offset into the four stored arrays is 64-bit.
+// =====================================================================================================================
+constexpr int KLD_WG = 1024, KLD_WAVES = KLD_WG / 64;
+constexpr int KLD_PAD = 192;   // the per-index arrays of a workgroup: three elements per lane
+struct KnotLdlArgs {
+    const KnotLdlTables* lt;
+    const double* hvals;          // [batch][nnz_h]
+    const double* dx;             // [batch][n] or null
+    double* factor;               // [batch][N][KL_DOUBLES]
+    int32_t* pivots;              // [batch][N][KL_N]: pivot words (knot_ldl.h)
+    double* e;                    // [batch][N][KL_N]
+    double* o;                    // [batch][N][KL_N]
+    int32_t* inertia;             // [batch][N][3]
+    int32_t* status;              // [batch][N]
+    double floor;
+    int32_t N, n;
+    HessRunDims hd;
+};
+struct alignas(16) KnotLdlLds {
+    double a[KL_DOUBLES];                    // the packed lower triangle: the block, then L and D in place
+    double x0[KLD_PAD], x1[KLD_PAD];         // the pivot column(s) before the scaling
+    int32_t ipiv[KLD_PAD], perm[KLD_PAD], kind[KLD_PAD];
+};
+static_assert(sizeof(KnotLdlLds) <= 160 * 1024 && sizeof(KnotLdlLds) - sizeof(double) * KL_DOUBLES <= 20200, "one workgroup per CU; what lies beside the triangle");
+static_assert(KL_N <= KLD_PAD && KL_N <= KLD_WG, "one thread per index");
+
+__device__ __forceinline__ PlMax knot_ldl_wave_max(PlMax a) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) a = pl_max_join(a, PlMax{__shfl_xor(a.v, o, 64), __shfl_xor(a.at, o, 64), __shfl_xor(a.bad, o, 64)});
+    return a;
+}
+
+// The factorisation of s.a in place; KL_OK or KL_NONFINITE.  Every thread takes every branch the same way: what it branches on comes from
+// LDS words that no thread writes between the barrier in front of the search and B1.  The caller puts a barrier behind it.
+__device__ __forceinline__ int knot_ldl_factor(KnotLdlLds& s, int tid, int& pos, int& neg, int& zero) {
+    constexpr int N = KL_N;
+    const int lane = tid & 63, wave = tid >> 6;
+    pos = neg = zero = 0;
+    if (tid < N) s.perm[tid] = tid;
+    int k = 0;
+    while (k < N) {
+        const int kc = pl_col(N, k);
+        const double akk = s.a[kc];
+        PlMax cm = pl_max_none();
+        for (int i = k + 1 + lane; i < N; i += 64) cm = pl_max_join(cm, pl_max_of(s.a[kc + i - k], i));
+        cm = knot_ldl_wave_max(cm);
+        int bad = cm.bad | (minres_finite(akk) ? 0 : 1);
+        const double absakk = pl_abs(akk), colmax = cm.v < 0.0 ? 0.0 : cm.v;
+        int kp = k, kstep = 1;
+        double arr = 0.0;
+        bool zero_column = false;
+        if (!bad) {
+            if (pl_column_is_zero(absakk, colmax)) zero_column = true;
+            else if (!pl_keep_diagonal(absakk, colmax)) {
+                const int imax = cm.at, pc = pl_col(N, imax);
+                PlMax rm = pl_max_none();
+                for (int j = k + lane; j < imax; j += 64) rm = pl_max_join(rm, pl_max_of(s.a[pl_at(N, imax, j)], j));
+                for (int i = imax + 1 + lane; i < N; i += 64) rm = pl_max_join(rm, pl_max_of(s.a[pc + i - imax], i));
+                rm = knot_ldl_wave_max(rm);
+                arr = s.a[pc];
+                bad = rm.bad | (minres_finite(arr) ? 0 : 1);
+                if (!bad) { const PlPivot pv = pl_choose(k, imax, absakk, colmax, rm.v, pl_abs(arr)); kp = pv.kp; kstep = pv.kstep; }
+            }
+        }
+        if (__builtin_amdgcn_readfirstlane(bad)) return KL_NONFINITE;
+        if (__builtin_amdgcn_readfirstlane(int(zero_column))) {   // the column is its own L column; nothing moves, nothing is updated: no barrier
+            ++zero;
+            if (tid == 0) { s.ipiv[k] = k + 1; s.kind[k] = PL_ONE; }
+            k = k + 1;
+            continue;
+        }
+        kp = __builtin_amdgcn_readfirstlane(kp);
+        kstep = __builtin_amdgcn_readfirstlane(kstep);
+        const int kk = k + kstep - 1, knc = pl_col(N, kk), base = k + kstep;
+        lds_barrier();                                                        // B1
+        if (kp != kk) {
+            if (tid < N && tid != kp) {
+                const int pcol = pl_col(N, kp);
+                int p, q;
+                if (tid < kk) { p = pl_at(N, kk, tid); q = pl_at(N, kp, tid); }          // the rows kk and kp of a column in front (and, of a 2x2 pivot, of column k)
+                else if (tid == kk) { p = knc; q = pcol; }                               // the two diagonal elements
+                else if (tid < kp) { p = knc + tid - kk; q = pl_at(N, kp, tid); }        // column kk between them against row kp
+                else { p = knc + tid - kk; q = pcol + tid - kp; }                        // the two columns below kp
+                const double u = s.a[p];
+                s.a[p] = s.a[q];
+                s.a[q] = u;
+            } else if (tid == kp) {
+                const int32_t u = s.perm[kk];
+                s.perm[kk] = s.perm[kp];
+                s.perm[kp] = u;
+            }
+            lds_barrier();                                                    // B2
+        }
+        if (kstep == 1) {
+            const double d = kp == k ? akk : arr;
+            if (d > 0.0) ++pos; else ++neg;
+            if (tid == 0) { s.ipiv[k] = kp + 1; s.kind[k] = PL_ONE; }
+            const int i = base + tid;
+            if (i < N) { const double x = s.a[kc + i - k]; s.x0[i] = x; s.a[kc + i - k] = pl_l1(x, d); }
+        } else {
+            ++pos; ++neg;
+            if (tid == 0) { s.ipiv[k] = s.ipiv[k + 1] = -(kp + 1); s.kind[k] = PL_FIRST; s.kind[k + 1] = PL_SECOND; }
+            const PlBlock blk = pl_block(s.a[kc], s.a[kc + 1], s.a[knc]);
+            const int i = base + tid;
+            if (i < N) {
+                const double x0 = s.a[kc + i - k], x1 = s.a[knc + i - kk];
+                s.x0[i] = x0; s.x1[i] = x1;
+                s.a[kc + i - k] = pl_w_first(blk, x0, x1);
+                s.a[knc + i - kk] = pl_w_second(blk, x0, x1);
+            }
+        }
+        lds_barrier();                                                        // B3
+        for (int j = base + wave; j < N; j += KLD_WAVES) {
+            const int cj = pl_col(N, j) - j;                                  // (i, j) at cj + i
+            if (kstep == 1) {
+                const double lj = s.a[kc + j - k];
+                for (int i = j + lane; i < N; i += 64) s.a[cj + i] = pl_update1(s.a[cj + i], s.x0[i], lj);
+            } else {
+                const double w0 = s.a[kc + j - k], w1 = s.a[knc + j - kk];
+                for (int i = j + lane; i < N; i += 64) s.a[cj + i] = pl_update2(s.a[cj + i], s.x0[i], s.x1[i], w0, w1);
+            }
+        }
+        lds_barrier();                                                        // B4
+        k = base;
+    }
+    return KL_OK;
+}
+
+__global__ __launch_bounds__(KLD_WG) void hipnlp_kkt_block_factor_kernel(KnotLdlArgs a) {
+    __shared__ KnotLdlLds s;
+    constexpr int N = KL_N;
+    const int tid = threadIdx.x, k = blockIdx.x, b = blockIdx.y;
+    const int64_t rec = int64_t(b) * a.N + k;                                  // the (trajectory, knot) record of the four stored arrays
+    const bool with_dx = a.dx != nullptr;
+    const double dx_c = (with_dx && tid < N) ? a.dx[int64_t(b) * a.n + int64_t(NXK) * k + tid] : 0.0;
+    // ---- assembly
+    for (int e = tid; e < KL_DOUBLES; e += KLD_WG) s.a[e] = 0.0;
+    lds_barrier();
+    const double* hv = a.hvals + int64_t(b) * a.hd.nnz_h + int64_t(a.hd.nnz_knot) * k;
+    const int cnt = a.hd.nnz_knot < KL_ENT_CAP ? a.hd.nnz_knot : KL_ENT_CAP;
+    for (int e = tid; e < cnt; e += KLD_WG) {
+        const int32_t at = a.lt->at[e];
+        if (at >= 0 && at < KL_DOUBLES) s.a[at] = hv[e];
+    }
+    lds_barrier();
+    if (tid < N) { const int p = pl_col(N, tid); s.a[p] = pl_diag_top(s.a[p], with_dx, dx_c, false, 0.0); }
+    lds_barrier();
+    // ---- factorisation
+    int pos, neg, zero;
+    const int status = knot_ldl_factor(s, tid, pos, neg, zero);
+    lds_barrier();
+    const bool good = status == KL_OK;
+    // ---- the stores: every word of the record, whatever the status
+    double* f = a.factor + rec * int64_t(KL_DOUBLES);
+    for (int e = tid; e < KL_DOUBLES; e += KLD_WG) f[e] = good ? s.a[e] : pl_nan();
+    if (tid < N) {
+        const int64_t i = rec * int64_t(N) + tid;
+        double ev = pl_nan(), ov = pl_nan();
+        int32_t word = kl_word(tid + 1, tid, PL_ONE);
+        if (good) {
+            const int kind = s.kind[tid], ci = pl_col(N, tid);
+            word = kl_word(s.ipiv[tid], s.perm[tid], kind);
+            ov = 0.0;
+            if (kind == PL_ONE) ev = kl_floored_inverse(s.a[ci], a.floor);
+            else if (kind == PL_FIRST) { const KlAbsInv2 q = kl_abs_inverse2(s.a[ci], s.a[ci + 1], s.a[pl_col(N, tid + 1)], a.floor); ev = q.e0; ov = q.o; }
+            else { const int cp = pl_col(N, tid - 1); ev = kl_abs_inverse2(s.a[cp], s.a[cp + 1], s.a[ci], a.floor).e1; }
+        }
+        a.pivots[i] = word;
+        a.e[i] = ev;
+        a.o[i] = ov;
+    }
+    if (tid == 0) {
+        a.inertia[rec * 3 + 0] = good ? pos : 0; a.inertia[rec * 3 + 1] = good ? neg : 0; a.inertia[rec * 3 + 2] = good ? zero : 0;
+        a.status[rec] = status;
+    }
+}
+
+// One knot's  z = P^T L^-T |D|^-1 L^-1 P r  by ONE wave (knot_ldl.h APPLY): lane l holds the elements l, l + 64, l + 128 in three named
+// registers.  f, words, e, o: of this knot's record.  src(j): r_j, dst(j, v): z_j = v, j an index of the knot's 189.
+constexpr int KLA_AHEAD = 4;   // columns / rows of L requested ahead of the one in use
+template <class Src, class Dst>
+__device__ __forceinline__ void knot_ldl_apply_wave(const double* __restrict__ f, const int32_t* __restrict__ words, const double* __restrict__ e, const double* __restrict__ o,
+                                                    int lane, const Src& src, const Dst& dst) {
+    constexpr int N = KL_N, U = KLA_AHEAD;
+    const int i0 = lane, i1 = lane + 64, i2 = lane + 128;
+    const bool on2 = i2 < N;
+    const int32_t w0 = words[i0], w1 = words[i1], w2 = on2 ? words[i2] : kl_word(0, 0, PL_ONE);
+    const double e0 = e[i0], e1 = e[i1], e2 = on2 ? e[i2] : 0.0;
+    const double o0 = o[i0], o1 = o[i1], o2 = on2 ? o[i2] : 0.0;
+    const bool good = kl_good(minres_readlane(e0, 0));
+    const int p0 = kl_word_perm(w0), p1 = kl_word_perm(w1), p2 = kl_word_perm(w2);
+    auto put = [&](int p, double v) __attribute__((always_inline)) { if (p < N) dst(p, v); };   // (the words are the caller's memory: nothing is addressed by them unchecked)
+    if (!good) {
+        put(p0, pl_nan()); put(p1, pl_nan());
+        if (on2) put(p2, pl_nan());
+        return;
+    }
+    // which indices are the first of a 2x2 block: one 64-bit mask per register, the same in every lane
+    const uint64_t f0 = __ballot(kl_word_kind(w0) == PL_FIRST), f1 = __ballot(kl_word_kind(w1) == PL_FIRST), f2 = __ballot(on2 && kl_word_kind(w2) == PL_FIRST);
+    auto is_first = [&](int i) __attribute__((always_inline)) { const int r = i >> 6; return int(((r == 0 ? f0 : (r == 1 ? f1 : f2)) >> (i & 63)) & 1); };
+    double y0 = src(p0 < N ? p0 : 0), y1 = src(p1 < N ? p1 : 0), y2 = on2 ? src(p2 < N ? p2 : 0) : 0.0;
+    // ---- forward: column k of L, (i, k) at c + i; the loads of KLA_AHEAD columns are in flight
+    auto column = [&](int k, double (&l)[3]) __attribute__((always_inline)) {
+        const int c = pl_col(N, k) - k;
+        l[0] = i0 > k ? f[c + i0] : 0.0;
+        l[1] = i1 > k ? f[c + i1] : 0.0;
+        l[2] = (on2 && i2 > k) ? f[c + i2] : 0.0;
+    };
+    double cur[U][3], nxt[U][3];
+#pragma unroll
+    for (int u = 0; u < U; ++u) column(u, cur[u]);
+    for (int kb = 0; kb < N; kb += U) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) column(kb + U + u, nxt[u]);            // (beyond 188: no lane is below the diagonal, nothing is read)
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int k = kb + u;
+            if (k >= N) break;
+            const int kr = k >> 6, kl = k & 63;
+            const int lo = k + 1 + is_first(k);
+            const double yk = minres_readlane(kr == 0 ? y0 : (kr == 1 ? y1 : y2), kl);
+            if (i0 >= lo) y0 = pl_axpy(y0, cur[u][0], yk);
+            if (i1 >= lo) y1 = pl_axpy(y1, cur[u][1], yk);
+            if (on2 && i2 >= lo) y2 = pl_axpy(y2, cur[u][2], yk);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) { cur[u][0] = nxt[u][0]; cur[u][1] = nxt[u][1]; cur[u][2] = nxt[u][2]; }
+    }
+    // ---- the diagonal: element i needs i + 1 and i - 1 of y and i - 1 of o, all taken before any is changed
+    {
+        const int nl = (lane + 1) & 63, pl = (lane + 63) & 63;
+        const double n0 = __shfl(y0, nl, 64), n1 = __shfl(y1, nl, 64), n2 = __shfl(y2, nl, 64);
+        const double q0 = __shfl(y0, pl, 64), q1 = __shfl(y1, pl, 64), q2 = __shfl(y2, pl, 64);
+        const double g0 = __shfl(o0, pl, 64), g1 = __shfl(o1, pl, 64), g2 = __shfl(o2, pl, 64);
+        const double up0 = lane == 63 ? n1 : n0, up1 = lane == 63 ? n2 : n1, up2 = lane == 63 ? 0.0 : n2;   // (lane 63's next element is lane 0's of the next register)
+        const double dn0 = lane == 0 ? 0.0 : q0, dn1 = lane == 0 ? q0 : q1, dn2 = lane == 0 ? q1 : q2;
+        const double od0 = lane == 0 ? 0.0 : g0, od1 = lane == 0 ? g0 : g1, od2 = lane == 0 ? g1 : g2;
+        y0 = kl_diag3(e0, y0, o0, up0, od0, dn0);
+        y1 = kl_diag3(e1, y1, o1, up1, od1, dn1);
+        y2 = on2 ? kl_diag3(e2, y2, o2, up2, od2, dn2) : 0.0;
+    }
+    // ---- backward: row i of L, (i, k) at rb_k + i
+    const int rb0 = pl_col(N, i0) - i0, rb1 = pl_col(N, i1) - i1, rb2 = on2 ? pl_col(N, i2) - i2 : 0;
+    auto row = [&](int i, double (&l)[3]) __attribute__((always_inline)) {
+        l[0] = (i >= 0 && i0 < i) ? f[rb0 + i] : 0.0;
+        l[1] = (i >= 0 && i1 < i) ? f[rb1 + i] : 0.0;
+        l[2] = (i >= 0 && on2 && i2 < i) ? f[rb2 + i] : 0.0;
+    };
+#pragma unroll
+    for (int u = 0; u < U; ++u) row(N - 1 - u, cur[u]);
+    for (int ib = N - 1; ib >= 0; ib -= U) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) row(ib - U - u, nxt[u]);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int i = ib - u;
+            if (i < 0) break;
+            const int ir = i >> 6, il = i & 63;
+            const int hi = i - 1 - (i > 0 ? is_first(i - 1) : 0);                 // i is the second index of a 2x2 block where i - 1 is the first
+            const double yi = minres_readlane(ir == 0 ? y0 : (ir == 1 ? y1 : y2), il);
+            if (i0 <= hi) y0 = pl_axpy(y0, cur[u][0], yi);
+            if (i1 <= hi) y1 = pl_axpy(y1, cur[u][1], yi);
+            if (on2 && i2 <= hi) y2 = pl_axpy(y2, cur[u][2], yi);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) { cur[u][0] = nxt[u][0]; cur[u][1] = nxt[u][1]; cur[u][2] = nxt[u][2]; }
+    }
+    put(p0, y0); put(p1, y1);
+    if (on2) put(p2, y2);
+}
+
+// M^-1 [r_top; r_bottom] in ONE launch on the operator's grid: the first wave applies the knot's stored factor, the other three take the
+// diagonal part — the rows minres_owned gives the knot's 256 threads (both row slots of every thread), and at the last knot the six
+// globals — by minres_precond, the expression of the MINRES first launch.
+struct KnotLdlStored {
+    const double* factor;         // [batch][N][KL_DOUBLES]
+    const int32_t* pivots;        // [batch][N][KL_N]
+    const double* e;              // [batch][N][KL_N]
+    const double* o;              // [batch][N][KL_N]
+};
+struct KnotLdlApplyArgs {
+    const JprodTables* jt;
+    KnotLdlStored st;
+    const double* minv_top;       // [batch][n]: read at the six globals only
+    const double* minv_bottom;    // [batch][m]
+    const double* r_top;          // [batch][n]
+    const double* r_bottom;       // [batch][m]
+    double* z_top;
+    double* z_bottom;
+    int32_t N, n, m;
+};
+__global__ __launch_bounds__(JP_WG)
+void hipnlp_kkt_block_apply_kernel(KnotLdlApplyArgs a) {
+    const int tid = threadIdx.x, k = blockIdx.x, b = blockIdx.y, N = a.N;
+    if (tid < 64) {
+        const int64_t rec = int64_t(b) * N + k;
+        const double* r = a.r_top + int64_t(b) * a.n + int64_t(NXK) * k;
+        double* z = a.z_top + int64_t(b) * a.n + int64_t(NXK) * k;
+        knot_ldl_apply_wave(a.st.factor + rec * int64_t(KL_DOUBLES), a.st.pivots + rec * int64_t(KL_N), a.st.e + rec * int64_t(KL_N), a.st.o + rec * int64_t(KL_N), tid,
+                            [&](int j) __attribute__((always_inline)) { return r[j]; }, [&](int j, double v) __attribute__((always_inline)) { z[j] = v; });
+        return;
+    }
+    const int pv = pair_variant(k, N);
+    const int64_t mb = int64_t(b) * a.m;
+    for (int q = tid - 64; q < JP_ROW_CAP; q += JP_WG - 64) {
+        const int32_t ra = a.jt->row_a[pv][q];
+        if (ra == G_NONE) continue;
+        const int64_t i = mb + ra + a.jt->row_b[pv][q] * k;
+        a.z_bottom[i] = minres_precond(true, a.minv_bottom[i], a.r_bottom[i]);
+    }
+    if (k == N - 1 && tid - 64 < NXG) {
+        const int64_t i = int64_t(b) * a.n + int64_t(NXK) * N + (tid - 64);
+        a.z_top[i] = minres_precond(true, a.minv_top[i], a.r_top[i]);
+    }
+}
+
+// The MINRES first launch (hipnlp_kkt_minres_first_kernel: its text, element for element) with the block top: the workgroup's 189 new r2
+// elements go through LDS, the first wave applies the knot's stored factor to them, and the threads take M^-1 r2 of their top element from
+// LDS in place of minv_top * r2.  The rows, and the six globals at the last knot, are the diagonal's as there; the chain of the partial of
+// r2 . M^-1 r2 is the same: top element, first row, second row, then the tree.
+__global__ __launch_bounds__(JP_WG)
+void hipnlp_kkt_minres_block_first_kernel(MinresArgs s, KnotLdlStored st) {
+    __shared__ double tree[JP_WG / 64];
+    __shared__ double buf[1];
+    __shared__ double r2s[KLD_PAD], ys[KLD_PAD];
+    const int tid = threadIdx.x, b = blockIdx.y, k = blockIdx.x;
+    const bool init = s.it == 0;
+    if (!init && s.rec_in(b).status != MINRES_RUNNING) return;
+    const MinresOwned o = minres_owned_of(s, tid, k);
+    const int32_t e[3] = {o.top, o.row[0], o.row[1]};
+    const bool block_top = tid < NXK;                                           // (o.top is then NXK k + tid)
+    double in_y[3], in_r2[3], in_m[3];   // (the start: in_y is b)
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const bool on = e[q] >= 0;
+        const int64_t i = (q == 0 ? int64_t(b) * s.n : int64_t(b) * s.m) + (on ? e[q] : 0);
+        const double* y = init ? (q == 0 ? s.rhs_top : s.rhs_bottom) : (q == 0 ? s.top(MR_Y, 0) : s.bottom(MR_Y, 0));
+        in_y[q] = on ? y[i] : 0.0;
+        in_r2[q] = (on && !init) ? (q == 0 ? s.top(MR_R2, 0) : s.bottom(MR_R2, 0))[i] : 0.0;
+        in_m[q] = (on && !(q == 0 && block_top)) ? (q == 0 ? s.minv_top : s.minv_bottom)[i] : 0.0;
+    }
+    double c2 = 0.0;
+    if (!init) {
+        const double* const part[1] = {s.part_a + int64_t(b) * s.N};
+        double alfa[1];
+        minres_sum_staged<1>(part, s.N, buf, alfa);
+        c2 = minres_div(alfa[0], s.rec_in(b).beta);
+    }
+    double r[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        if (e[q] < 0) continue;
+        const int64_t i = (q == 0 ? int64_t(b) * s.n : int64_t(b) * s.m) + e[q];
+        auto vec = [&](int v) __attribute__((always_inline)) { return q == 0 ? s.top(v, 0) : s.bottom(v, 0); };
+        if (init) {
+            r[q] = in_y[q];
+            vec(MR_W)[i] = 0.0; vec(MR_W2)[i] = 0.0; (q == 0 ? s.z_top : s.z_bottom)[i] = 0.0;
+            vec(MR_R1)[i] = r[q];
+        } else {
+            r[q] = minres_new_r2(c2, in_r2[q], in_y[q]);
+            vec(MR_R1)[i] = in_r2[q];
+        }
+        vec(MR_R2)[i] = r[q];
+    }
+    if (block_top) r2s[tid] = r[0];
+    __syncthreads();
+    if (tid < 64) {
+        const int64_t rec = int64_t(b) * s.N + k;
+        knot_ldl_apply_wave(st.factor + rec * int64_t(KL_DOUBLES), st.pivots + rec * int64_t(KL_N), st.e + rec * int64_t(KL_N), st.o + rec * int64_t(KL_N), tid,
+                            [&](int j) __attribute__((always_inline)) { return r2s[j]; }, [&](int j, double v) __attribute__((always_inline)) { ys[j] = v; });
+    }
+    __syncthreads();
+    double acc = 0.0;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        if (e[q] < 0) continue;
+        const int64_t i = (q == 0 ? int64_t(b) * s.n : int64_t(b) * s.m) + e[q];
+        const double ym = (q == 0 && block_top) ? ys[tid] : minres_precond(true, in_m[q], r[q]);
+        (q == 0 ? s.top(MR_Y, 0) : s.bottom(MR_Y, 0))[i] = ym;
+        acc = fm_fma(r[q], ym, acc);
+    }
+    const double sum = workgroup_tree(acc, tree);
+    if (tid == 0) s.part_b[int64_t(b) * s.N + k] = sum;
+}
+
+
 // Throughput variant only (4 waves; the latency variant sums inside the knot kernel, see pub_step): f[b] = sum over knots and
 // terms, cost_terms[b][t] = sum over knots.  One workgroup per trajectory.  Thread (group g = tid / 16, column c = tid % 16) sums
 // column c of the knots g, g + 16, ...: all its loads are independent and issued together (ONE memory round trip), then a fixed
@@ -2104,6 +2502,7 @@ struct hipnlp_handle {
     double* d_minres = nullptr;          // the workspace of hipnlp_kkt_minres_device: vectors, partials, scalar records (one allocation)
     int32_t* h_minres_status = nullptr;  // pinned [batch]: the statuses a check_every > 0 solve looks at
     SaddleDiagTables* d_dt = nullptr;    // hipnlp_kkt_diag_precond_device: the diagonal positions of the Hessian block, uploaded at the first call
+    KnotLdlTables* d_klt = nullptr;      // hipnlp_kkt_block_factor_device: the packed places of a knot block's entries (knot_ldl.h), uploaded at the first call
     std::string err;
 };
 
@@ -2158,7 +2557,7 @@ static void free_all(hipnlp_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->dev);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* dptrs[] = {h->d_tb, h->d_ctpl, h->d_ctpl_of_b, h->d_healed, h->d_x, h->d_pk, h->d_cost_knot, h->d_gp, h->d_cost_pub, h->d_out, h->d_ht, h->d_sigma, h->d_hess, h->d_hflag, h->d_htrash, h->d_lt, h->d_vt, h->d_jt, h->d_jtt, h->d_jdot, h->d_minres, h->d_dt};
+    void* dptrs[] = {h->d_tb, h->d_ctpl, h->d_ctpl_of_b, h->d_healed, h->d_x, h->d_pk, h->d_cost_knot, h->d_gp, h->d_cost_pub, h->d_out, h->d_ht, h->d_sigma, h->d_hess, h->d_hflag, h->d_htrash, h->d_lt, h->d_vt, h->d_jt, h->d_jtt, h->d_jdot, h->d_minres, h->d_dt, h->d_klt};
     for (void* q : dptrs) if (q) (void)hipFree(q);
     void* hptrs[] = {h->h_x, h->h_out, h->h_hess, h->h_hflag, h->h_sl, h->h_minres_status};
     for (void* q : hptrs) if (q) (void)hipHostFree(q);
@@ -3572,6 +3971,112 @@ int hipnlp_kkt_diag_precond_device(hipnlp_handle* h, const double* hess_values_d
     HIP_TRY(h, hipGetLastError());
     return HIPNLP_OK;
 }
+// ---- the block top of a preconditioner: per-knot L |D| L^T (include/hipnlp.h; knot_ldl.h) ----------------------------------------------------
+static int kkt_block_prepare(hipnlp_handle* h, const char* who) {
+    if (h->is_front) { h->err = std::string(who) + ": a multi-device handle (hipnlp_multi_create) serves the host-buffer calls only"; return HIPNLP_E_UNSUPPORTED; }
+    if (const int rc = whole_horizon_only(h, who, "a row of g has entries in the blocks of two knots, the periodicity rows need both horizon ends")) return rc;
+    if (const int rc = jprod_prepare(h, who)) return rc;
+    if (const int rc = hvp_prepare(h, who)) return rc;   // (the Hessian layout, and that its entries stay inside a knot record)
+    if (!h->HL.ldl_fits()) { h->err = std::string(who) + ": a knot block of the Hessian has more entries than the block factorisation places"; return HIPNLP_E_UNSUPPORTED; }
+    return HIPNLP_OK;
+}
+static KnotLdlStored kkt_block_stored(const double* factor, const int32_t* pivots, const double* e, const double* o) { return {factor, pivots, e, o}; }
+int hipnlp_kkt_block_bytes(const hipnlp_handle* h, int64_t* bytes_out) {
+    if (!h || !bytes_out) return HIPNLP_E_INVALID;
+    const int64_t recs = int64_t(h->batch) * h->L.N;
+    bytes_out[0] = recs * KL_DOUBLES * int64_t(sizeof(double));
+    bytes_out[1] = recs * KL_N * int64_t(sizeof(int32_t));
+    bytes_out[2] = bytes_out[3] = recs * KL_N * int64_t(sizeof(double));
+    return HIPNLP_OK;
+}
+int hipnlp_kkt_block_factor_device(hipnlp_handle* h, const double* hess_values_dev, const double* dx_dev, double floor, double* factor_dev, int32_t* pivots_dev, double* e_dev,
+                                   double* o_dev, int32_t* inertia_dev, int32_t* status_dev, void* stream) {
+    if (!h) return HIPNLP_E_INVALID;
+    if (const char* e = kl_factor_call_error(hess_values_dev, floor, factor_dev, pivots_dev, e_dev, o_dev, inertia_dev, status_dev)) {
+        h->err = std::string("hipnlp_kkt_block_factor_device: ") + e;
+        return HIPNLP_E_INVALID;
+    }
+    if (const int rc = kkt_block_prepare(h, "hipnlp_kkt_block_factor_device")) return rc;
+    if (!h->d_klt) {
+        KnotLdlTables* t = new KnotLdlTables();
+        h->HL.fill_ldl_tables(*t);
+        const int rc = upload_table(h, reinterpret_cast<void**>(&h->d_klt), t, sizeof(KnotLdlTables), "block factorisation table");
+        delete t;
+        if (rc != HIPNLP_OK) return rc;
+    }
+    HIP_TRY(h, hipSetDevice(h->dev));
+    KnotLdlArgs a;
+    a.lt = h->d_klt; a.hvals = hess_values_dev; a.dx = dx_dev; a.factor = factor_dev; a.pivots = pivots_dev; a.e = e_dev; a.o = o_dev;
+    a.inertia = inertia_dev; a.status = status_dev; a.floor = floor; a.N = h->L.N; a.n = h->L.n; a.hd = hess_run_dims(h);
+    hipLaunchKernelGGL(hipnlp_kkt_block_factor_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(KLD_WG), 0, stream ? hipStream_t(stream) : h->stream, a);
+    HIP_TRY(h, hipGetLastError());
+    return HIPNLP_OK;
+}
+int hipnlp_kkt_block_apply_device(hipnlp_handle* h, const double* factor_dev, const int32_t* pivots_dev, const double* e_dev, const double* o_dev, const double* minv_top_dev,
+                                  const double* minv_bottom_dev, const double* r_top_dev, const double* r_bottom_dev, double* z_top_dev, double* z_bottom_dev, void* stream) {
+    if (!h) return HIPNLP_E_INVALID;
+    if (const char* e = kl_apply_call_error(factor_dev, pivots_dev, e_dev, o_dev, minv_top_dev, minv_bottom_dev, r_top_dev, r_bottom_dev, z_top_dev, z_bottom_dev)) {
+        h->err = std::string("hipnlp_kkt_block_apply_device: ") + e;
+        return HIPNLP_E_INVALID;
+    }
+    if (const int rc = kkt_block_prepare(h, "hipnlp_kkt_block_apply_device")) return rc;
+    HIP_TRY(h, hipSetDevice(h->dev));
+    KnotLdlApplyArgs a;
+    a.jt = h->d_jt; a.st = kkt_block_stored(factor_dev, pivots_dev, e_dev, o_dev); a.minv_top = minv_top_dev; a.minv_bottom = minv_bottom_dev;
+    a.r_top = r_top_dev; a.r_bottom = r_bottom_dev; a.z_top = z_top_dev; a.z_bottom = z_bottom_dev; a.N = h->L.N; a.n = h->L.n; a.m = h->L.m;
+    hipLaunchKernelGGL(hipnlp_kkt_block_apply_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(JP_WG), 0, stream ? hipStream_t(stream) : h->stream, a);
+    HIP_TRY(h, hipGetLastError());
+    return HIPNLP_OK;
+}
+// hipnlp_kkt_minres_device's launches with hipnlp_kkt_minres_block_first_kernel in the place of the first kernel
+int hipnlp_kkt_minres_block_device(hipnlp_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev, const double* dc_dev,
+                                   const double* factor_dev, const int32_t* pivots_dev, const double* e_dev, const double* o_dev, const double* minv_top_dev,
+                                   const double* minv_bottom_dev, const double* rhs_top_dev, const double* rhs_bottom_dev, double* sol_top_dev, double* sol_bottom_dev, double rtol,
+                                   int max_iterations, int check_every, int32_t* iterations_dev, double* residual_dev, int32_t* status_dev, void* stream) {
+    if (!h) return HIPNLP_E_INVALID;
+    if (const char* e = kl_minres_call_error(hess_values_dev, jac_values_dev, factor_dev, pivots_dev, e_dev, o_dev, minv_top_dev, minv_bottom_dev, rhs_top_dev, rhs_bottom_dev,
+                                             sol_top_dev, sol_bottom_dev, iterations_dev, residual_dev, status_dev, rtol, max_iterations, check_every)) {
+        h->err = std::string("hipnlp_kkt_minres_block_device: ") + e;
+        return HIPNLP_E_INVALID;
+    }
+    if (const int rc = minres_prepare(h, "hipnlp_kkt_minres_block_device")) return rc;
+    if (const int rc = kkt_block_prepare(h, "hipnlp_kkt_minres_block_device")) return rc;
+    hipStream_t st = stream ? hipStream_t(stream) : h->stream;
+    const Layout& L = h->L;
+    MinresArgs s;
+    s.jt = h->d_jt; s.minv_top = minv_top_dev; s.minv_bottom = minv_bottom_dev; s.rhs_top = rhs_top_dev; s.rhs_bottom = rhs_bottom_dev;
+    s.z_top = sol_top_dev; s.z_bottom = sol_bottom_dev;
+    char* base = reinterpret_cast<char*>(h->d_minres);
+    s.vec = reinterpret_cast<double*>(base);
+    s.part_a = reinterpret_cast<double*>(base + minres_vec_bytes(h));
+    s.part_b = reinterpret_cast<double*>(base + minres_vec_bytes(h) + minres_part_bytes(h));
+    s.rec = reinterpret_cast<MinresRec*>(base + minres_vec_bytes(h) + 2 * minres_part_bytes(h));
+    s.iterations = iterations_dev; s.residual = residual_dev; s.status = status_dev;
+    s.rtol = rtol; s.N = L.N; s.n = L.n; s.m = L.m; s.batch = h->batch; s.maxit = max_iterations; s.it = 0;
+    const KnotLdlStored blk = kkt_block_stored(factor_dev, pivots_dev, e_dev, o_dev);
+    double* v = s.vec + int64_t(MR_V) * h->batch * (int64_t(L.n) + L.m);
+    double* y = s.vec + int64_t(MR_Y) * h->batch * (int64_t(L.n) + L.m);
+    const KktArgs a = kkt_args(h, hess_values_dev, jac_values_dev, dx_dev, dc_dev, v, v + int64_t(h->batch) * L.n, y, y + int64_t(h->batch) * L.n);
+    const dim3 grid(unsigned(h->nk), unsigned(h->batch)), wg(JP_WG);
+    hipLaunchKernelGGL(hipnlp_kkt_minres_block_first_kernel, grid, wg, 0, st, s, blk);
+    hipLaunchKernelGGL(hipnlp_kkt_minres_second_kernel, grid, wg, 0, st, s);
+    HIP_TRY(h, hipGetLastError());
+    for (int it = 1; it <= max_iterations; ++it) {
+        s.it = it;
+        hipLaunchKernelGGL(hipnlp_kkt_minres_apply_kernel, grid, wg, 0, st, a, s);
+        hipLaunchKernelGGL(hipnlp_kkt_minres_block_first_kernel, grid, wg, 0, st, s, blk);
+        hipLaunchKernelGGL(hipnlp_kkt_minres_second_kernel, grid, wg, 0, st, s);
+        HIP_TRY(h, hipGetLastError());
+        if (check_every > 0 && it % check_every == 0 && it < max_iterations) {   // the only synchronisation: is any trajectory still running?
+            HIP_TRY(h, hipMemcpyAsync(h->h_minres_status, status_dev, size_t(h->batch) * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+            HIP_TRY(h, hipStreamSynchronize(st));
+            bool running = false;
+            for (int b = 0; b < h->batch; ++b) running = running || h->h_minres_status[b] == MINRES_RUNNING;
+            if (!running) break;
+        }
+    }
+    return HIPNLP_OK;
+}
 // how a handle in auto mode (hipnlp_set_hessian_early_run(h, -1)) came to its choice
 enum { HESS_WHY_UNDECIDED = 0, HESS_WHY_FORCED = 1, HESS_WHY_NOT_ARMABLE = 2, HESS_WHY_NUMA_SAME = 3, HESS_WHY_NUMA_OTHER = 4, HESS_WHY_MEASURED = 5 };
 // NUMA node of the CPU the calling thread runs on (Linux sysfs: the node whose cpulist holds it); -1: not known / one node only says nothing
@@ -4417,7 +4922,23 @@ int hipnlp_host_release_auto_ranges(void) {
 // library or of the caller) may lie inside a range some handle registered by itself for an array that has been FREED since — the
 // allocator handed its addresses out again, the runtime still believes the old registration.  Those registrations are conveniences
 // the handles re-create whenever they see their arrays again: all are released and the copy is tried once more.
+// The runtime does NOT always refuse: where the buffer only OVERLAPS such a range (it begins in front of it, or reaches beyond its end)
+// the copy can go through the dead registration's mapping and end in an illegal memory access, which no retry repairs.  So the ranges
+// handles registered by themselves that overlap the host side of the copy are released BEFORE it: the library's own buffers are never
+// an array a handle registered, so an overlap can only be a registration of freed memory.
+static void release_auto_ranges_overlapping(const void* p, size_t bytes) {
+    std::vector<char*> stale;
+    {
+        std::lock_guard<std::mutex> lock(g_ranges_mutex);
+        const char* q = static_cast<const char*>(p);
+        for (const HostRange& r : g_ranges)
+            if (r.owner != nullptr && q < r.host + r.bytes && r.host < q + bytes) stale.push_back(r.host);
+    }
+    for (char* sp : stale) (void)hipnlp_host_unregister(sp);
+}
 extern "C" hipError_t hipnlp_internal_memcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    if (kind == hipMemcpyHostToDevice) release_auto_ranges_overlapping(src, bytes);
+    else if (kind == hipMemcpyDeviceToHost) release_auto_ranges_overlapping(dst, bytes);
     hipError_t e = hipMemcpy(dst, src, bytes, kind);
     if (e == hipErrorInvalidValue) {
         (void)hipGetLastError();

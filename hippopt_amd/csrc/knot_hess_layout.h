@@ -11,6 +11,7 @@
 
 #include "knot_hess_body.h"
 #include "knot_hvp.h"
+#include "knot_ldl.h"
 #include "layout.h"
 
 namespace hipnlp {
@@ -135,6 +136,12 @@ struct HessLayout {
             hvp_error = "a knot block of the Hessian has " + std::to_string(hv_touch.size()) + " touches, at most " + std::to_string(kmax) +
                         " per variable: more than the Hessian-vector kernels stage (" + std::to_string(HVP_WORD_CAP) + " / " + std::to_string((1 << HVP_CNT_BITS) - 1) + ")";
         }
+    }
+    // the device table of the per-knot dense factorisation (knot_ldl.h): row and column of the entry at every block position as its place
+    // in the packed lower triangle of order NXK.  ldl_fits: every entry lies inside the knot record (hvp_ok) and the block within the table.
+    bool ldl_fits() const { return hvp_ok && nnz_knot <= KL_ENT_CAP; }
+    void fill_ldl_tables(KnotLdlTables& t) const {
+        for (int p = 0; p < KL_ENT_CAP; ++p) t.at[p] = p < nnz_knot ? pl_at(KL_N, lrow[size_t(p)], lcol[size_t(p)]) : -1;
     }
     long knot_base(int k) const { return long(nnz_knot) * k; }
     long couple_base() const { return long(nnz_knot) * N; }

@@ -30,6 +30,7 @@ EXPORTS = [
     "hipnlp_eval_lagrangian_grad_device", "hipnlp_eval_hess_vec_device", "hipnlp_hess_times_device",
     "hipnlp_jac_times_device", "hipnlp_jac_transpose_times_device", "hipnlp_kkt_times_device", "hipnlp_kkt_minres_device", "hipnlp_kkt_minres_reserve",
     "hipnlp_kkt_diag_precond_device",
+    "hipnlp_kkt_block_bytes", "hipnlp_kkt_block_factor_device", "hipnlp_kkt_block_apply_device", "hipnlp_kkt_minres_block_device",
     "hipnlp_eval_pinned", "hipnlp_set_prefetch", "hipnlp_set_early_outputs", "hipnlp_set_host_timing", "hipnlp_host_register", "hipnlp_host_unregister",
     "hipnlp_multi_create", "hipnlp_multi_plan", "hipnlp_multi_info", "hipnlp_multi_breakdown", "hipnlp_multi_set_threads",
     "hipnlp_host_breakdown", "hipnlp_set_auto_register", "hipnlp_host_stats", "hipnlp_set_constant_jacobian", "hipnlp_forget_jac_destination", "hipnlp_jac_constant_mask", "hipnlp_host_release_auto_ranges",
@@ -238,6 +239,11 @@ def load_library(path=None):
         lib.hipnlp_kkt_minres_reserve.argtypes = [vp, C.POINTER(C.c_int64)]
     if hasattr(lib, "hipnlp_kkt_diag_precond_device"):
         lib.hipnlp_kkt_diag_precond_device.argtypes = [vp] * 5 + [C.c_double] + [vp] * 3
+    if hasattr(lib, "hipnlp_kkt_block_factor_device"):
+        lib.hipnlp_kkt_block_bytes.argtypes = [vp, C.POINTER(C.c_int64)]
+        lib.hipnlp_kkt_block_factor_device.argtypes = [vp] * 3 + [C.c_double] + [vp] * 7
+        lib.hipnlp_kkt_block_apply_device.argtypes = [vp] * 12
+        lib.hipnlp_kkt_minres_block_device.argtypes = [vp] * 15 + [C.c_double, C.c_int, C.c_int] + [vp] * 4
     _libs[path] = lib
     return lib
 
@@ -663,6 +669,44 @@ class HipNlp:
         vp = C.c_void_p
         self._check(self.lib.hipnlp_kkt_diag_precond_device(self.h, vp(hess_values_ptr or None), vp(jac_values_ptr or None), vp(dx_ptr or None), vp(dc_ptr or None),
                                                             float(floor), vp(minv_top_ptr or None), vp(minv_bottom_ptr or None), vp(stream or None)))
+
+    # ---- the block top of the preconditioner: a dense L |D| L^T per knot block (knot_ldl.h) ---------------------------------------------------
+    def kkt_block_bytes(self):
+        """(factor, pivots, e, o): the bytes of the four stored arrays of kkt_block_factor_device for this handle's batch and horizon
+        (hipnlp_kkt_block_bytes; the factor is 143 640 B per knot and trajectory)"""
+        out = (C.c_int64 * 4)()
+        self._check(self.lib.hipnlp_kkt_block_bytes(self.h, out))
+        return tuple(int(v) for v in out)
+
+    def kkt_block_factor_device(self, hess_values_ptr, factor_ptr, pivots_ptr, e_ptr, o_ptr, inertia_ptr, status_ptr, dx_ptr=0, floor=1e-10, stream=0):
+        """Factor every knot's block of H + diag dx (dx optional) by Bunch-Kaufman pivoting in ONE launch, one workgroup per (knot,
+        trajectory) (hipnlp_kkt_block_factor_device): factor [batch][N][17955], pivots [batch][N][189] int32 (pivot words), e and o
+        [batch][N][189] (|D|^-1 with every |eigenvalue| floored), inertia [batch][N][3] int32 (+, -, 0) and status [batch][N] int32
+        (0 factored, 2 data not finite: that knot's factor, e and o are NaN); floor > 0; asynchronous on `stream`"""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_kkt_block_factor_device(self.h, vp(hess_values_ptr or None), vp(dx_ptr or None), float(floor), vp(factor_ptr or None), vp(pivots_ptr or None),
+                                                            vp(e_ptr or None), vp(o_ptr or None), vp(inertia_ptr or None), vp(status_ptr or None), vp(stream or None)))
+
+    def kkt_block_apply_device(self, factor_ptr, pivots_ptr, e_ptr, o_ptr, minv_top_ptr, minv_bottom_ptr, r_top_ptr, r_bottom_ptr, z_top_ptr, z_bottom_ptr, stream=0):
+        """[z_top; z_bottom] = M^-1 [r_top; r_bottom] in ONE launch (hipnlp_kkt_block_apply_device): the knot blocks from the stored
+        factor, the six globals from minv_top, the bottom from minv_bottom (kkt_diag_precond_device's outputs); the outputs may not alias
+        the inputs"""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_kkt_block_apply_device(self.h, vp(factor_ptr or None), vp(pivots_ptr or None), vp(e_ptr or None), vp(o_ptr or None), vp(minv_top_ptr or None),
+                                                           vp(minv_bottom_ptr or None), vp(r_top_ptr or None), vp(r_bottom_ptr or None), vp(z_top_ptr or None),
+                                                           vp(z_bottom_ptr or None), vp(stream or None)))
+
+    def kkt_minres_block_device(self, hess_values_ptr, jac_values_ptr, factor_ptr, pivots_ptr, e_ptr, o_ptr, minv_top_ptr, minv_bottom_ptr, rhs_top_ptr, rhs_bottom_ptr,
+                                sol_top_ptr, sol_bottom_ptr, iterations_ptr, residual_ptr, status_ptr, dx_ptr=0, dc_ptr=0, rtol=1e-8, max_iterations=200, check_every=16,
+                                stream=0):
+        """kkt_minres_device with the block preconditioner of kkt_block_factor_device (hipnlp_kkt_minres_block_device): minv_top then
+        serves the six globals only; everything else as there"""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_kkt_minres_block_device(self.h, vp(hess_values_ptr or None), vp(jac_values_ptr or None), vp(dx_ptr or None), vp(dc_ptr or None),
+                                                            vp(factor_ptr or None), vp(pivots_ptr or None), vp(e_ptr or None), vp(o_ptr or None), vp(minv_top_ptr or None),
+                                                            vp(minv_bottom_ptr or None), vp(rhs_top_ptr or None), vp(rhs_bottom_ptr or None), vp(sol_top_ptr or None),
+                                                            vp(sol_bottom_ptr or None), float(rtol), int(max_iterations), int(check_every), vp(iterations_ptr or None),
+                                                            vp(residual_ptr or None), vp(status_ptr or None), vp(stream or None)))
 
     def kkt_minres_reserve(self):
         """allocate the handle's MINRES workspace now (otherwise: on the first solve); returns its size in bytes"""

@@ -361,7 +361,8 @@ int hipnlp_set_auto_register(hipnlp_handle* h, int on);
 /* Releases every range that handles of this process registered by themselves (returns how many); the handles register their arrays
  * again when they next see them twice in a row.  For a caller about to free arrays it passed to hipnlp_eval: memory that is freed while
  * a registration of it is alive and then handed out again by the allocator confuses the HIP runtime — a hipMemcpy from such memory is
- * refused with "invalid argument" (the library's own copies release the ranges and retry when that happens). */
+ * refused with "invalid argument", or goes through the dead mapping and ends in an illegal memory access (the library's own copies
+ * release the ranges that overlap their host buffer before they copy, and all of them and retry after an "invalid argument"). */
 int hipnlp_host_release_auto_ranges(void);
 /* Counters of the host-buffer path: out[0] arrays auto-registered so far, out[1] stale-mapping fallbacks, out[2] ranges currently
  * auto-registered, out[3] evaluations so far (kernel launches), out[4] caller arrays filled with the constant Jacobian entries so far,
@@ -586,6 +587,49 @@ int hipnlp_kkt_minres_reserve(hipnlp_handle* h, int64_t* bytes_out);
  * a finite number > 0. */
 int hipnlp_kkt_diag_precond_device(hipnlp_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev,
                                    const double* dc_dev, double floor, double* minv_top_dev, double* minv_bottom_dev, void* stream);
+
+/* A block top for that preconditioner, and the inertia of every knot's block of H + diag d_x (hippopt_amd/csrc/knot_ldl.h):
+ *
+ *     M^-1 = blockdiag_k( P_k^T L_k^-T |D_k|^-1 L_k^-1 P_k )  (+)  diag(minv_top of the six globals)  (+)  diag(minv_bottom)
+ *
+ * The Hessian of the Lagrangian is block diagonal by knot (189 variables each; a periodicity coupling of the horizon ends, where the
+ * pattern has one, is left out of the blocks), so one workgroup holds a block's packed lower triangle (17 955 doubles) in its LDS and
+ * factors it by Bunch-Kaufman partial pivoting, the algorithm and the pinned choices of hipnlp_pose_kkt_ldl_device.  |D| replaces every
+ * eigenvalue of D by max(|lambda|, floor): M is symmetric positive definite whatever the inertia of the blocks.  minv_top_dev (read at the
+ * six globals only) and minv_bottom_dev are hipnlp_kkt_diag_precond_device's outputs.
+ *   hipnlp_kkt_block_bytes           bytes_out[4]: the bytes of factor_dev, pivots_dev, e_dev, o_dev for this handle's batch and horizon
+ *                                    (the factor is 143 640 B per knot and trajectory)
+ *   hipnlp_kkt_block_factor_device   ONE launch, a workgroup of 1 024 threads per (knot, trajectory): assembles H_k + diag d_x,k (dx_dev
+ *                                    may be NULL) from the Hessian run, factors it, and stores per (trajectory, knot): factor_dev
+ *                                    [batch][N][17955] (L and D, packed lower triangle by columns, every interchange applied to whole
+ *                                    rows of L), pivots_dev [batch][N][189] int32 (bits 0..15 LAPACK's ipiv as int16, bits 16..23 the
+ *                                    permutation, bits 24..25: 0 a 1x1 pivot, 1 / 2 the first / second index of a 2x2 block), e_dev and
+ *                                    o_dev [batch][N][189] (|D|^-1: its diagonal, and the coupling of index i to i + 1), inertia_dev
+ *                                    [batch][N][3] int32 (positive, negative, zero) and status_dev [batch][N] int32: 0 factored; 2 a value
+ *                                    that is not finite — that knot's factor, e and o are NaN in every word, its inertia (0, 0, 0).  A
+ *                                    pivot column that is exactly zero counts as ONE zero and the factorisation goes on.  Nothing is
+ *                                    retried or regularised.  Every word of the six arrays is written.
+ *   hipnlp_kkt_block_apply_device    ONE launch: [z_top; z_bottom] = M^-1 [r_top; r_bottom] from the stored arrays; a knot with status
+ *                                    2 yields NaN for its 189 elements.  The outputs may not alias the inputs.
+ *   hipnlp_kkt_minres_block_device   hipnlp_kkt_minres_device with this M^-1: its arguments plus the four stored arrays; the first
+ *                                    launch of every iteration applies the knot's factor in its first wave.  Statuses as there: a knot
+ *                                    with status 2 ends its trajectory with status 2.
+ * Every element is one fixed chain of fused multiply-adds: the same bits on every launch, at every batch position.  HIPNLP_E_INVALID: a
+ * null handle or required pointer (all but dx_dev / dc_dev), a floor that is not a finite number > 0, rtol < 0, max_iterations < 0,
+ * check_every < 0 — refused before anything is launched.  HIPNLP_E_UNSUPPORTED as hipnlp_kkt_diag_precond_device.  Measured:
+ * profiles/r16_kkt_block.txt (tools/kkt_block_probe.py).  NOT claimed: that an interior-point step is cheap with it; systems with
+ * diagonals a factor 1e-4 smaller than U[1, 2] were not seen to converge with either preconditioner. */
+int hipnlp_kkt_block_bytes(const hipnlp_handle* h, int64_t* bytes_out /*[4]*/);
+int hipnlp_kkt_block_factor_device(hipnlp_handle* h, const double* hess_values_dev, const double* dx_dev /*or NULL*/, double floor, double* factor_dev,
+                                   int32_t* pivots_dev, double* e_dev, double* o_dev, int32_t* inertia_dev, int32_t* status_dev, void* stream);
+int hipnlp_kkt_block_apply_device(hipnlp_handle* h, const double* factor_dev, const int32_t* pivots_dev, const double* e_dev, const double* o_dev,
+                                  const double* minv_top_dev, const double* minv_bottom_dev, const double* r_top_dev, const double* r_bottom_dev, double* z_top_dev,
+                                  double* z_bottom_dev, void* stream);
+int hipnlp_kkt_minres_block_device(hipnlp_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev /*or NULL*/,
+                                   const double* dc_dev /*or NULL*/, const double* factor_dev, const int32_t* pivots_dev, const double* e_dev, const double* o_dev,
+                                   const double* minv_top_dev, const double* minv_bottom_dev, const double* rhs_top_dev, const double* rhs_bottom_dev,
+                                   double* sol_top_dev, double* sol_bottom_dev, double rtol, int max_iterations, int check_every, int32_t* iterations_dev,
+                                   double* residual_dev, int32_t* status_dev, void* stream);
 
 /* Sharded variant (multi-GPU): the handle owns knots [knot_begin, knot_end).  Outputs are
  * shard-local and contiguous so that one RCCL all-gather reassembles them:

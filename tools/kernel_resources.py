@@ -2,6 +2,8 @@
 """Register / scratch / LDS figures of every kernel in a built libhipnlp.so, read from the code-object metadata of the library
 ITSELF (what the GPU box will load), not from a fresh compile: the .hip_fatbin section holds one clang offload bundle per
 translation unit; its gfx950 entries are ELF code objects whose NT_AMDGPU_METADATA note lists every kernel.
+The kernels of the per-knot block preconditioner (KKT_BLOCK) have a table of their own: kernel_resources() lists every other kernel,
+kernel_resources(table="kkt_block") these three.
     python tools/kernel_resources.py [path/to/libhipnlp.so]"""
 import os
 import re
@@ -13,6 +15,8 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LLVM = os.environ.get("HIPNLP_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+# the table of the block preconditioner of the KKT solve (hipnlp.hip; knot_ldl.h)
+KKT_BLOCK = ("hipnlp_kkt_block_factor_kernel", "hipnlp_kkt_block_apply_kernel", "hipnlp_kkt_minres_block_first_kernel")
 
 
 def code_objects(lib_path, tmp):
@@ -38,8 +42,8 @@ def code_objects(lib_path, tmp):
         pos = i + 1
 
 
-def kernel_resources(lib_path=None):
-    """{demangled-ish kernel name: {"vgpr", "sgpr", "scratch", "lds", "wg"}}"""
+def kernel_resources(lib_path=None, table="main"):
+    """{demangled-ish kernel name: {"vgpr", "sgpr", "scratch", "lds", "wg"}} of one table: "main" (every kernel but KKT_BLOCK's) or "kkt_block" (these)"""
     lib_path = lib_path or os.path.join(ROOT, "hippopt_amd", "lib", "libhipnlp.so")
     res = {}
     with tempfile.TemporaryDirectory(prefix="hipnlp_res_") as tmp:
@@ -61,13 +65,16 @@ def kernel_resources(lib_path=None):
                         while args and args[-1] == ("b", "0"):   # (trailing `false` defaults are left out: <0,4> is <0,4,false>)
                             args.pop()
                         short += "<" + ",".join(("true" if v == "1" else "false") if k == "b" else v for k, v in args) + ">"
+                if (short.split("<")[0] in KKT_BLOCK) != (table == "kkt_block"):
+                    continue
                 res[short] = {"vgpr": num("vgpr_count"), "agpr": int(blk.split()[0]), "sgpr": num("sgpr_count"), "scratch": num("private_segment_fixed_size"),
                               "lds": num("group_segment_fixed_size"), "wg": num("max_flat_workgroup_size")}
     return res
 
 
 if __name__ == "__main__":
-    r = kernel_resources(sys.argv[1] if len(sys.argv) > 1 else None)
-    for k in sorted(r):
-        v = r[k]
-        print("%-34s VGPRs %3d (+%d AGPRs)  SGPRs %3d  scratch %4d B/lane  LDS %6d B  workgroup %4d" % (k, v["vgpr"], v["agpr"], v["sgpr"], v["scratch"], v["lds"], v["wg"]))
+    for table in ("main", "kkt_block"):
+        r = kernel_resources(sys.argv[1] if len(sys.argv) > 1 else None, table)
+        for k in sorted(r):
+            v = r[k]
+            print("%-34s VGPRs %3d (+%d AGPRs)  SGPRs %3d  scratch %4d B/lane  LDS %6d B  workgroup %4d" % (k, v["vgpr"], v["agpr"], v["sgpr"], v["scratch"], v["lds"], v["wg"]))
