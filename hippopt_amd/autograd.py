@@ -23,6 +23,8 @@
     z = K.solve(b_top, b_bottom, minv=K.diagonal_preconditioner())   # ... with the diagonal M^-1 built in ONE launch (hipnlp_kkt_diag_precond_device)
     M = K.block_preconditioner()                           # per-knot L |D| L^T of H + diag dx (hipnlp_kkt_block_factor_device) + that diagonal; M.inertia
     z = K.solve(b_top, b_bottom, minv=M)                   # ... MINRES with the block top (hipnlp_kkt_minres_block_device)
+    P = K.convexify()                                      # per-knot inertia-correcting ladder (hipnlp_kkt_block_ladder_device): P.delta, P.tries, P.quasi_definite
+    z = P.values.solve(b_top, b_bottom, minv=P)            # ... MINRES on the convexified operator P.values with the exact inverse of its top blocks
 
 The forward pass is hipnlp_eval_device with grad f and jac g left out; the backward pass is the Lagrangian gradient
 sigma grad f + J^T lambda with sigma = df, lambda = dg (zeros for an output whose gradient is None): the Jacobian never reaches memory.
@@ -323,6 +325,61 @@ class KKTValues:
         top, bottom = self.diagonal_preconditioner(floor)
         return KKTBlockPreconditioner(self, factor, pivots, e, o, inertia, status, top, bottom)
 
+    def convexify(self, delta_init=1e-4, kappa=8.0, max_tries=16, floor=1e-10):
+        """KKTBlockPreconditioner of the CONVEXIFIED operator: every knot climbs an inertia-correcting ladder on its own block until
+        H_k + diag dx_k + delta_k I is positive definite, and the returned object carries the operator that goes with it.  What it does:
+        (1) ONE ladder launch (hipnlp_kkt_block_ladder_device, one workgroup per knot and trajectory): try 0 is block_preconditioner's
+        factorisation; try t >= 1 factors the block again, whole, with delta_t = delta_init kappa^(t-1) on its 189 diagonal elements; a
+        knot stops at its first try with the inertia (189, 0, 0), or at try max_tries (0 .. 16).  (2) dx' = dx + delta_k on knot k's 189
+        variables, the six globals unchanged, dx = None counting as zeros (plain torch).  (3) the diagonal launch of
+        diagonal_preconditioner on K' = self.with_diagonals(dx', dc), for the bottom and the six globals.
+        The result has block_preconditioner's attributes — of every knot's LAST try — and .delta [batch, N], .tries [batch, N] int32,
+        .status [batch, N] (0 factored; 2 data not finite; 3 ladder exhausted: the inertia of try max_tries is stored and is not
+        (189, 0, 0)), .values = K', the operator to solve on: pre.values.solve(b_top, b_bottom, minv=pre), and .quasi_definite [batch]
+        bool: every knot status 0 with inertia (189, 0, 0), dx > 0 at the six globals, and dc given and > 0 everywhere.
+        GUARANTEED where .quasi_definite holds and the Hessian pattern couples no two knots: the top block of .values is positive
+        definite, so .values is symmetric quasi-definite with inertia exactly (n, m, 0) — the figure IPOPT's regularisation loop asks
+        for — without a factorisation of K'; every pivot of the stored factors is 1x1 and positive, so apply() is the inverse of the top
+        blocks of .values, not of an absolute value of them.  (A pattern with a periodicity coupling of the horizon ends has entries
+        outside every block: they are in .values and in no delta_k.)
+        NOT guaranteed: that delta is minimal in IPOPT's sense — this is a sufficient and conservative correction: IPOPT needs only the
+        Hessian reduced to the null space of J positive definite and adds ONE delta to the whole top block, while here every knot makes
+        its whole block positive definite, which can take more; nor that MINRES converges on .values, with this preconditioner or any
+        other.  delta_init and kappa default to IPOPT's first_hessian_perturbation and perturb_inc_fact; nobody has tuned them here, nor
+        floor.  Cost: (tries + 1) factorisations for the slowest knot of the launch; measured: profiles/r17_kkt_ladder.txt.
+        max_tries = 0 is block_preconditioner with delta 0 and tries 0.  Nothing is synchronised: all attributes are device tensors."""
+        torch, nlp = _torch(), self.nlp
+        floor = _checked_floor(floor)
+        if not (isinstance(max_tries, numbers.Integral) and not isinstance(max_tries, bool) and 0 <= max_tries <= 16):
+            raise ValueError("max_tries: an integer in 0 .. 16, not %r" % (max_tries,))
+        if not (isinstance(delta_init, numbers.Real) and not isinstance(delta_init, bool) and 0.0 < delta_init < float("inf")):
+            raise ValueError("delta_init: a finite real number > 0, not %r" % (delta_init,))
+        if not (isinstance(kappa, numbers.Real) and not isinstance(kappa, bool) and 1.0 < kappa < float("inf")):
+            raise ValueError("kappa: a finite real number > 1, not %r" % (kappa,))
+        dev, nbytes = self.hess.device, nlp.engine.kkt_block_bytes()
+        N = (nlp.n - 6) // self.ORDER                                          # knots: n = 189 N + the six globals
+        factor = torch.empty((nlp.batch, N, nbytes[0] // (8 * nlp.batch * N)), dtype=torch.float64, device=dev)
+        pivots = torch.empty((nlp.batch, N, nbytes[1] // (4 * nlp.batch * N)), dtype=torch.int32, device=dev)
+        e = torch.empty((nlp.batch, N, nbytes[2] // (8 * nlp.batch * N)), dtype=torch.float64, device=dev)
+        assert factor.shape[2] == self.ORDER * (self.ORDER + 1) // 2 and pivots.shape[2] == e.shape[2] == self.ORDER
+        o = torch.empty_like(e)
+        inertia = torch.empty((nlp.batch, N, 3), dtype=torch.int32, device=dev)
+        status = torch.empty((nlp.batch, N), dtype=torch.int32, device=dev)
+        delta = torch.empty((nlp.batch, N), dtype=torch.float64, device=dev)
+        tries = torch.empty((nlp.batch, N), dtype=torch.int32, device=dev)
+        nlp._on_current_stream(lambda s: nlp.engine.kkt_block_ladder_device(self.hess.data_ptr(), factor.data_ptr(), pivots.data_ptr(), e.data_ptr(), o.data_ptr(),
+                                                                            inertia.data_ptr(), status.data_ptr(), delta.data_ptr(), tries.data_ptr(),
+                                                                            dx_ptr=self.dx.data_ptr() if self.dx is not None else 0, floor=floor,
+                                                                            delta_init=float(delta_init), kappa=float(kappa), max_tries=int(max_tries), stream=s))
+        dx = torch.zeros((nlp.batch, nlp.n), dtype=torch.float64, device=dev) if self.dx is None else self.dx.clone()
+        dx[:, :self.ORDER * N] += delta.repeat_interleave(self.ORDER, dim=1)
+        convex = self.with_diagonals(dx, self.dc)
+        top, bottom = convex.diagonal_preconditioner(floor)
+        wanted = torch.tensor([self.ORDER, 0, 0], dtype=torch.int32, device=dev)
+        quasi = (status == 0).all(dim=1) & (inertia == wanted).all(dim=2).all(dim=1) & (dx[:, self.ORDER * N:] > 0.0).all(dim=1)
+        quasi = quasi & (self.dc > 0.0).all(dim=1) if self.dc is not None else torch.zeros_like(quasi)
+        return KKTBlockPreconditioner(convex, factor, pivots, e, o, inertia, status, top, bottom, delta=delta, tries=tries, quasi_definite=quasi)
+
     def solve(self, rhs_top, rhs_bottom, rtol=1e-8, maxiter=200, minv=None, check_every=16):
         """KKTSolution(top [batch, n], bottom [batch, m], iterations [batch] int32, residual [batch], status [batch] int32) of
         K [top; bottom] = [rhs_top; rhs_bottom] by preconditioned MINRES from a zero start, resident on the device
@@ -387,12 +444,15 @@ class KKTBlockPreconditioner:
     .pivots [batch, N, 189] int32 (pivot words: bits 0..15 LAPACK's ipiv, 16..23 the permutation, 24..25 the index's place in D), .e / .o
     [batch, N, 189] (|D|^-1), .inertia [batch, N, 3] int32, .status [batch, N] int32, .top_diagonal [batch, n] (used at the six globals)
     and .bottom [batch, m] (the diagonal preconditioner's).  apply(r_top, r_bottom) is ONE launch (hipnlp_kkt_block_apply_device);
-    KKTValues.solve(minv=this) runs MINRES with it.  Tied to the value runs and diagonals it was built from."""
+    KKTValues.solve(minv=this) runs MINRES with it.  Tied to the value runs and diagonals it was built from.
+    What KKTValues.convexify built has, beside these, .delta [batch, N], .tries [batch, N] int32 and .quasi_definite [batch] bool (None
+    on what block_preconditioner built), and its .values is the CONVEXIFIED operator — the one to solve on with it."""
 
-    def __init__(self, values, factor, pivots, e, o, inertia, status, top_diagonal, bottom):
+    def __init__(self, values, factor, pivots, e, o, inertia, status, top_diagonal, bottom, *, delta=None, tries=None, quasi_definite=None):
         self.nlp, self.values = values.nlp, values
         self.factor, self.pivots, self.e, self.o, self.inertia, self.status = factor, pivots, e, o, inertia, status
         self.top_diagonal, self.bottom = top_diagonal, bottom
+        self.delta, self.tries, self.quasi_definite = delta, tries, quasi_definite
 
     def apply(self, r_top, r_bottom):
         """(z_top [batch, n], z_bottom [batch, m]) = M^-1 [r_top; r_bottom], one launch; a knot with status 2 yields NaN for its 189 elements"""

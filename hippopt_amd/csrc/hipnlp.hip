@@ -1880,6 +1880,8 @@ __device__ __forceinline__ PlMax knot_ldl_wave_max(PlMax a) {
 
 // The factorisation of s.a in place; KL_OK or KL_NONFINITE.  Every thread takes every branch the same way: what it branches on comes from
 // LDS words that no thread writes between the barrier in front of the search and B1.  The caller puts a barrier behind it.
+// (WHO: one instantiation per calling kernel, so that each kernel's code is compiled as if it were the function's only caller.)
+template <int WHO = 0>
 __device__ __forceinline__ int knot_ldl_factor(KnotLdlLds& s, int tid, int& pos, int& neg, int& zero) {
     constexpr int N = KL_N;
     const int lane = tid & 63, wave = tid >> 6;
@@ -2020,6 +2022,79 @@ __global__ __launch_bounds__(KLD_WG) void hipnlp_kkt_block_factor_kernel(KnotLdl
     if (tid == 0) {
         a.inertia[rec * 3 + 0] = good ? pos : 0; a.inertia[rec * 3 + 1] = good ? neg : 0; a.inertia[rec * 3 + 2] = good ? zero : 0;
         a.status[rec] = status;
+    }
+}
+
+// The inertia-correcting ladder of knot_ldl.h (LADDER), climbed by every (knot, trajectory) on its own: the factor kernel's mapping, LDS and
+// factorisation inside a loop of at most 1 + PL_MAX_TRIES tries — assemble with the try's delta, factor, decide.  The decision is taken on
+// the status and the inertia that knot_ldl_factor returns identical in every thread, so every wave meets the same barriers and leaves the
+// loop at the same try.  After the loop the factor kernel's stores, of the last try, plus that try's delta and number.  No workgroup waits
+// for another, no atomics, nothing leaves the CU before the stores.
+struct KnotLdlLadderArgs {
+    KnotLdlArgs f;
+    double delta_init, kappa;
+    double* delta;                // [batch][N]
+    int32_t* tries;               // [batch][N]
+    int32_t max_tries;
+};
+__global__ __launch_bounds__(KLD_WG) void hipnlp_kkt_block_ladder_kernel(KnotLdlLadderArgs la) {
+    __shared__ KnotLdlLds s;
+    constexpr int N = KL_N;
+    const KnotLdlArgs& a = la.f;
+    const int tid = threadIdx.x, k = blockIdx.x, b = blockIdx.y;
+    const int64_t rec = int64_t(b) * a.N + k;
+    const bool with_dx = a.dx != nullptr;
+    const double dx_c = (with_dx && tid < N) ? a.dx[int64_t(b) * a.n + int64_t(NXK) * k + tid] : 0.0;
+    const double* hv = a.hvals + int64_t(b) * a.hd.nnz_h + int64_t(a.hd.nnz_knot) * k;
+    const int cnt = a.hd.nnz_knot < KL_ENT_CAP ? a.hd.nnz_knot : KL_ENT_CAP;
+    const int max_tries = la.max_tries < PL_MAX_TRIES ? la.max_tries : PL_MAX_TRIES;
+    double delta = 0.0;
+    int t = 0, status = KL_OK, pos = 0, neg = 0, zero = 0;
+    bool wanted = false;
+    for (int tr = 0; tr <= PL_MAX_TRIES; ++tr) {
+        // ---- assembly of try t: the whole block again, from the run in memory
+        for (int e = tid; e < KL_DOUBLES; e += KLD_WG) s.a[e] = 0.0;
+        lds_barrier();
+        for (int e = tid; e < cnt; e += KLD_WG) {
+            const int32_t at = a.lt->at[e];
+            if (at >= 0 && at < KL_DOUBLES) s.a[at] = hv[e];
+        }
+        lds_barrier();
+        if (tid < N) { const int p = pl_col(N, tid); s.a[p] = pl_diag_top(s.a[p], with_dx, dx_c, t > 0, delta); }
+        lds_barrier();
+        // ---- factorisation, whole whatever its pivots' signs
+        status = knot_ldl_factor<1>(s, tid, pos, neg, zero);
+        lds_barrier();
+        wanted =kl_inertia_wanted(pos, neg, zero);
+        if (!pl_ladder_goes_on(status, wanted, t, max_tries)) break;
+        ++t;
+        delta = pl_next_delta(t, delta, la.delta_init, la.kappa);
+    }
+    const bool good = status == KL_OK;
+    // ---- the stores: every word of the record, whatever the status
+    double* f = a.factor + rec * int64_t(KL_DOUBLES);
+    for (int e = tid; e < KL_DOUBLES; e += KLD_WG) f[e] = good ? s.a[e] : pl_nan();
+    if (tid < N) {
+        const int64_t i = rec * int64_t(N) + tid;
+        double ev = pl_nan(), ov = pl_nan();
+        int32_t word = kl_word(tid + 1, tid, PL_ONE);
+        if (good) {
+            const int kind = s.kind[tid], ci = pl_col(N, tid);
+            word = kl_word(s.ipiv[tid], s.perm[tid], kind);
+            ov = 0.0;
+            if (kind == PL_ONE) ev = kl_floored_inverse(s.a[ci], a.floor);
+            else if (kind == PL_FIRST) { const KlAbsInv2 q = kl_abs_inverse2(s.a[ci], s.a[ci + 1], s.a[pl_col(N, tid + 1)], a.floor); ev = q.e0; ov = q.o; }
+            else { const int cp = pl_col(N, tid - 1); ev = kl_abs_inverse2(s.a[cp], s.a[cp + 1], s.a[ci], a.floor).e1; }
+        }
+        a.pivots[i] = word;
+        a.e[i] = ev;
+        a.o[i] = ov;
+    }
+    if (tid == 0) {
+        a.inertia[rec * 3 + 0] = good ? pos : 0; a.inertia[rec * 3 + 1] = good ? neg : 0; a.inertia[rec * 3 + 2] = good ? zero : 0;
+        a.status[rec] = kl_ladder_final_status(status, wanted, max_tries);
+        la.delta[rec] = delta;
+        la.tries[rec] = t;
     }
 }
 
@@ -3980,6 +4055,15 @@ static int kkt_block_prepare(hipnlp_handle* h, const char* who) {
     if (!h->HL.ldl_fits()) { h->err = std::string(who) + ": a knot block of the Hessian has more entries than the block factorisation places"; return HIPNLP_E_UNSUPPORTED; }
     return HIPNLP_OK;
 }
+// the packed places of a knot block's entries on the device, uploaded at the first factorisation of either entry point
+static int kkt_block_table(hipnlp_handle* h) {
+    if (h->d_klt) return HIPNLP_OK;
+    KnotLdlTables* t = new KnotLdlTables();
+    h->HL.fill_ldl_tables(*t);
+    const int rc = upload_table(h, reinterpret_cast<void**>(&h->d_klt), t, sizeof(KnotLdlTables), "block factorisation table");
+    delete t;
+    return rc;
+}
 static KnotLdlStored kkt_block_stored(const double* factor, const int32_t* pivots, const double* e, const double* o) { return {factor, pivots, e, o}; }
 int hipnlp_kkt_block_bytes(const hipnlp_handle* h, int64_t* bytes_out) {
     if (!h || !bytes_out) return HIPNLP_E_INVALID;
@@ -3997,18 +4081,32 @@ int hipnlp_kkt_block_factor_device(hipnlp_handle* h, const double* hess_values_d
         return HIPNLP_E_INVALID;
     }
     if (const int rc = kkt_block_prepare(h, "hipnlp_kkt_block_factor_device")) return rc;
-    if (!h->d_klt) {
-        KnotLdlTables* t = new KnotLdlTables();
-        h->HL.fill_ldl_tables(*t);
-        const int rc = upload_table(h, reinterpret_cast<void**>(&h->d_klt), t, sizeof(KnotLdlTables), "block factorisation table");
-        delete t;
-        if (rc != HIPNLP_OK) return rc;
-    }
+    if (const int rc = kkt_block_table(h)) return rc;
     HIP_TRY(h, hipSetDevice(h->dev));
     KnotLdlArgs a;
     a.lt = h->d_klt; a.hvals = hess_values_dev; a.dx = dx_dev; a.factor = factor_dev; a.pivots = pivots_dev; a.e = e_dev; a.o = o_dev;
     a.inertia = inertia_dev; a.status = status_dev; a.floor = floor; a.N = h->L.N; a.n = h->L.n; a.hd = hess_run_dims(h);
     hipLaunchKernelGGL(hipnlp_kkt_block_factor_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(KLD_WG), 0, stream ? hipStream_t(stream) : h->stream, a);
+    HIP_TRY(h, hipGetLastError());
+    return HIPNLP_OK;
+}
+int hipnlp_kkt_block_ladder_device(hipnlp_handle* h, const double* hess_values_dev, const double* dx_dev, double floor, double delta_init, double kappa, int max_tries,
+                                   double* factor_dev, int32_t* pivots_dev, double* e_dev, double* o_dev, int32_t* inertia_dev, int32_t* status_dev, double* delta_dev,
+                                   int32_t* tries_dev, void* stream) {
+    if (!h) return HIPNLP_E_INVALID;
+    if (const char* e = kl_ladder_call_error(hess_values_dev, floor, delta_init, kappa, max_tries, factor_dev, pivots_dev, e_dev, o_dev, inertia_dev, status_dev, delta_dev,
+                                             tries_dev)) {
+        h->err = std::string("hipnlp_kkt_block_ladder_device: ") + e;
+        return HIPNLP_E_INVALID;
+    }
+    if (const int rc = kkt_block_prepare(h, "hipnlp_kkt_block_ladder_device")) return rc;
+    if (const int rc = kkt_block_table(h)) return rc;
+    HIP_TRY(h, hipSetDevice(h->dev));
+    KnotLdlLadderArgs a;
+    a.f.lt = h->d_klt; a.f.hvals = hess_values_dev; a.f.dx = dx_dev; a.f.factor = factor_dev; a.f.pivots = pivots_dev; a.f.e = e_dev; a.f.o = o_dev;
+    a.f.inertia = inertia_dev; a.f.status = status_dev; a.f.floor = floor; a.f.N = h->L.N; a.f.n = h->L.n; a.f.hd = hess_run_dims(h);
+    a.delta_init = delta_init; a.kappa = kappa; a.delta = delta_dev; a.tries = tries_dev; a.max_tries = max_tries;
+    hipLaunchKernelGGL(hipnlp_kkt_block_ladder_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(KLD_WG), 0, stream ? hipStream_t(stream) : h->stream, a);
     HIP_TRY(h, hipGetLastError());
     return HIPNLP_OK;
 }

@@ -40,6 +40,25 @@
 // t_i = fma(o_(i-1), y_(i-1), fma(o_i, y_(i+1), e_i y_i))  with o_(-1) = y_(-1) = y_189 = +0.0  (kl_diag3);  backward
 // t_k = fma(-L_ik, t_i, t_k)  for every row i DESCENDING;  z_perm[i] = t_i.  Each element takes one fused multiply-add per column, in
 // that order: the bits do not depend on the mapping.  A knot whose e_0 is NaN (KL_NONFINITE) yields pl_nan() for its 189 elements.
+//
+// LADDER (hipnlp_kkt_block_ladder_kernel; the test-only CPU emulation tests/kkt_ladder_emu): pose_ldl.h's inertia-correction ladder, climbed
+// by every knot on its own, inside the launch that holds its block.  Try 0 has delta = 0 and is the ASSEMBLY above, bit for bit.  Try
+// t >= 1 has delta_t = pl_next_delta(t, delta_(t-1), delta_init, kappa) — delta_1 = delta_init, then one rounded product per try — and is
+// a FULL re-assembly from the Hessian run in memory: every word +0.0, every stored entry through KnotLdlTables, then the diagonal
+// pl_diag_top(h, with_dx, dx_c, true, delta_t) = (H_cc + d_x,c) + delta_t, two roundings in that order.  Every try is a whole
+// factorisation (no exit at the first pivot that is not positive), so the inertia reported for a knot is complete whatever its status.
+// The ladder ends at the first try whose inertia is (189, 0, 0) (kl_inertia_wanted), at a try that is KL_NONFINITE, or at try max_tries;
+// factor, pivot words, e, o, inertia, delta and tries are the LAST try's.  Status (kl_ladder_final_status): KL_NONFINITE, else
+// KL_EXHAUSTED where max_tries > 0 and the inertia is still not wanted, else KL_OK.  There is no status 1: a zero pivot column counts as
+// one zero and the factorisation goes on — the inertia is then not wanted and the ladder climbs.  max_tries = 0: one factorisation, the
+// bits of the factor kernel, status KL_OK whatever the inertia.
+// WHAT A KL_OK OF A LADDER WITH max_tries > 0 MEANS: every pivot of the stored factor is 1x1 and positive (a Bunch-Kaufman 2x2 block has
+// a negative determinant, so it would have counted one negative), so |D| = D where no |d| is below the floor, o = 0, and APPLY from this
+// record is the inverse of H_k + diag d_x,k + delta_k I, not of an absolute value of it.  With every knot KL_OK, the six globals' d_x > 0
+// and d_c > 0, K' = [[A, J^T], [J, -diag d_c]] with A = blockdiag_k(H_k + d_x,k + delta_k I) (+) diag(d_x of the globals) is symmetric
+// quasi-definite: its inertia is (n, m, 0) without anybody factoring K'.  SUFFICIENT, NOT NECESSARY: IPOPT needs only the Hessian reduced
+// to the null space of J positive definite and perturbs with ONE delta for the whole matrix; a delta per knot on the whole block can be
+// larger than that needs, and is never smaller than what the block alone needs at the ladder's resolution (a factor kappa).
 #pragma once
 #include <cstdint>
 
@@ -53,7 +72,7 @@ namespace hipnlp {
 constexpr int KL_N = NXK;                                // 189: the order of a knot's block
 constexpr int KL_DOUBLES = KL_N * (KL_N + 1) / 2;        // 17 955
 constexpr int KL_ENT_CAP = (hk::COUNT + 255) / 256 * 256;   // entries of a knot's block of the Hessian run, at most
-enum { KL_OK = 0, KL_NONFINITE = 2 };
+enum { KL_OK = 0, KL_NONFINITE = 2, KL_EXHAUSTED = 3 };   // (no 1: a zero pivot column does not end a knot's factorisation)
 static_assert(KL_DOUBLES * int(sizeof(double)) == 143640 && KL_N <= 3 * 64 && KL_N < 256, "a packed block in one workgroup's LDS; three elements per lane; perm in eight bits");
 
 // The device table of the assembly (HessLayout::fill_ldl_tables): the packed place of the entry at every position of a knot's block, -1
@@ -96,12 +115,27 @@ HD double kl_diag3(double e_i, double y_i, double o_i, double y_up, double o_dn,
 // whether the knot's stored e says that it can be applied (KL_NONFINITE stores NaN in every word)
 HD bool kl_good(double e_first) { return e_first == e_first; }
 
+// ---- the ladder (the delta of a try: pl_next_delta; whether another try follows: pl_ladder_goes_on) --------------------------------------------
+HD bool kl_inertia_wanted(int pos, int neg, int zero) { return pos == KL_N && neg == 0 && zero == 0; }
+HD int kl_ladder_final_status(int status, bool wanted, int max_tries) { return status != KL_OK ? status : ((max_tries > 0 && !wanted) ? KL_EXHAUSTED : KL_OK); }
+static_assert(KL_NONFINITE == PL_NONFINITE && KL_EXHAUSTED == PL_EXHAUSTED && KL_OK == PL_OK, "pl_ladder_goes_on reads a knot's status");
+
 // ---- what the entry points refuse before anything is launched (nullptr: nothing) ------------------------------------------------------------
 inline const char* kl_factor_call_error(bool hess, double floor, bool factor, bool pivots, bool e, bool o, bool inertia, bool status) {
     if (!hess) return "hess_values_dev is required";
     if (!factor || !pivots || !e || !o) return "factor_dev, pivots_dev, e_dev and o_dev are required";
     if (!inertia || !status) return "inertia_dev and status_dev are required";
     if (!(floor > 0.0) || !minres_finite(floor)) return "floor must be a finite number > 0";
+    return nullptr;
+}
+// the ladder's entry point: the factor entry point's refusals, then its own (pl_factor_call_error's for the three ladder arguments)
+inline const char* kl_ladder_call_error(bool hess, double floor, double delta_init, double kappa, int max_tries, bool factor, bool pivots, bool e, bool o, bool inertia, bool status,
+                                        bool delta, bool tries) {
+    if (const char* r = kl_factor_call_error(hess, floor, factor, pivots, e, o, inertia, status)) return r;
+    if (!delta || !tries) return "delta_dev and tries_dev are required";
+    if (max_tries < 0 || max_tries > PL_MAX_TRIES) return "0 <= max_tries <= 16";
+    if (max_tries > 0 && (!minres_finite(delta_init) || !(delta_init > 0.0))) return "delta_init must be a finite number > 0 with max_tries > 0";
+    if (max_tries > 0 && (!minres_finite(kappa) || !(kappa > 1.0))) return "kappa must be a finite number > 1 with max_tries > 0";
     return nullptr;
 }
 inline const char* kl_apply_call_error(bool factor, bool pivots, bool e, bool o, bool minv_top, bool minv_bottom, bool r_top, bool r_bottom, bool z_top, bool z_bottom) {

@@ -31,6 +31,7 @@ EXPORTS = [
     "hipnlp_jac_times_device", "hipnlp_jac_transpose_times_device", "hipnlp_kkt_times_device", "hipnlp_kkt_minres_device", "hipnlp_kkt_minres_reserve",
     "hipnlp_kkt_diag_precond_device",
     "hipnlp_kkt_block_bytes", "hipnlp_kkt_block_factor_device", "hipnlp_kkt_block_apply_device", "hipnlp_kkt_minres_block_device",
+    "hipnlp_kkt_block_ladder_device",
     "hipnlp_eval_pinned", "hipnlp_set_prefetch", "hipnlp_set_early_outputs", "hipnlp_set_host_timing", "hipnlp_host_register", "hipnlp_host_unregister",
     "hipnlp_multi_create", "hipnlp_multi_plan", "hipnlp_multi_info", "hipnlp_multi_breakdown", "hipnlp_multi_set_threads",
     "hipnlp_host_breakdown", "hipnlp_set_auto_register", "hipnlp_host_stats", "hipnlp_set_constant_jacobian", "hipnlp_forget_jac_destination", "hipnlp_jac_constant_mask", "hipnlp_host_release_auto_ranges",
@@ -244,6 +245,8 @@ def load_library(path=None):
         lib.hipnlp_kkt_block_factor_device.argtypes = [vp] * 3 + [C.c_double] + [vp] * 7
         lib.hipnlp_kkt_block_apply_device.argtypes = [vp] * 12
         lib.hipnlp_kkt_minres_block_device.argtypes = [vp] * 15 + [C.c_double, C.c_int, C.c_int] + [vp] * 4
+    if hasattr(lib, "hipnlp_kkt_block_ladder_device"):
+        lib.hipnlp_kkt_block_ladder_device.argtypes = [vp] * 3 + [C.c_double] * 3 + [C.c_int] + [vp] * 9
     _libs[path] = lib
     return lib
 
@@ -686,6 +689,19 @@ class HipNlp:
         vp = C.c_void_p
         self._check(self.lib.hipnlp_kkt_block_factor_device(self.h, vp(hess_values_ptr or None), vp(dx_ptr or None), float(floor), vp(factor_ptr or None), vp(pivots_ptr or None),
                                                             vp(e_ptr or None), vp(o_ptr or None), vp(inertia_ptr or None), vp(status_ptr or None), vp(stream or None)))
+
+    def kkt_block_ladder_device(self, hess_values_ptr, factor_ptr, pivots_ptr, e_ptr, o_ptr, inertia_ptr, status_ptr, delta_ptr, tries_ptr, dx_ptr=0, floor=1e-10, delta_init=0.0,
+                                kappa=0.0, max_tries=0, stream=0):
+        """kkt_block_factor_device with an inertia-correcting ladder climbed by every knot on its own, in ONE launch
+        (hipnlp_kkt_block_ladder_device): try t >= 1 factors H_k + diag dx_k + delta_t I again, delta_1 = delta_init, delta_(t+1) = delta_t
+        kappa, until the block's inertia is (189, 0, 0) or try max_tries (0 .. 16) is reached.  The six arrays of kkt_block_factor_device
+        hold the knot's last try, delta [batch][N] and tries [batch][N] int32 its delta and number; status 0 factored (with max_tries > 0:
+        positive definite), 2 data not finite, 3 ladder exhausted.  max_tries = 0 is kkt_block_factor_device, bit for bit; delta_init
+        (finite, > 0) and kappa (finite, > 1) have no defaults and are required with max_tries > 0; asynchronous on `stream`"""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_kkt_block_ladder_device(self.h, vp(hess_values_ptr or None), vp(dx_ptr or None), float(floor), float(delta_init), float(kappa), int(max_tries),
+                                                            vp(factor_ptr or None), vp(pivots_ptr or None), vp(e_ptr or None), vp(o_ptr or None), vp(inertia_ptr or None),
+                                                            vp(status_ptr or None), vp(delta_ptr or None), vp(tries_ptr or None), vp(stream or None)))
 
     def kkt_block_apply_device(self, factor_ptr, pivots_ptr, e_ptr, o_ptr, minv_top_ptr, minv_bottom_ptr, r_top_ptr, r_bottom_ptr, z_top_ptr, z_bottom_ptr, stream=0):
         """[z_top; z_bottom] = M^-1 [r_top; r_bottom] in ONE launch (hipnlp_kkt_block_apply_device): the knot blocks from the stored

@@ -631,6 +631,36 @@ int hipnlp_kkt_minres_block_device(hipnlp_handle* h, const double* hess_values_d
                                    double* sol_top_dev, double* sol_bottom_dev, double rtol, int max_iterations, int check_every, int32_t* iterations_dev,
                                    double* residual_dev, int32_t* status_dev, void* stream);
 
+/* The inertia-correcting ladder of that factorisation, climbed by every knot on its own inside ONE launch (knot_ldl.h LADDER): the
+ * arguments and the six stored arrays of hipnlp_kkt_block_factor_device, plus delta_init, kappa, max_tries (0 .. 16) and two outputs,
+ * delta_dev [batch][N] and tries_dev [batch][N] int32.  Try 0 is hipnlp_kkt_block_factor_device's factorisation (delta = 0).  Try t >= 1
+ * assembles the block again from the Hessian run with delta_t added to all 189 diagonal elements — (H_cc + d_x,c) + delta_t, delta_1 =
+ * delta_init, delta_(t+1) = delta_t * kappa, one rounded product per try — and factors it again, whole.  A knot leaves the ladder at its
+ * first try with the inertia (189, 0, 0), at a try whose data is not finite, or at try max_tries; all eight arrays hold its LAST try.
+ * status_dev: 0 the stored factor has the inertia stored beside it, which with max_tries > 0 is (189, 0, 0); 2 a value that is not finite
+ * (NaN records as hipnlp_kkt_block_factor_device, inertia (0, 0, 0)); 3 the ladder was exhausted: the factor and the complete inertia of
+ * try max_tries are stored, and it is not (189, 0, 0).  There is no status 1: a pivot column that is exactly zero counts as one zero, the
+ * factorisation goes on, and the ladder climbs.  max_tries = 0 is one factorisation: the bits of hipnlp_kkt_block_factor_device in all
+ * six arrays, status 0 or 2, delta 0, tries 0 (delta_init and kappa are then not read).
+ *
+ * What status 0 with max_tries > 0 gives: every pivot is 1x1 and positive, so o = 0, e = 1 / d (where no d is below the floor), and
+ * hipnlp_kkt_block_apply_device / hipnlp_kkt_minres_block_device apply the INVERSE of H_k + diag d_x,k + delta_k I from this record.
+ * With every knot at status 0, d_x > 0 at the six globals and d_c > 0 everywhere, the matrix
+ *     K' = [ A   J^T ; J   -diag d_c ],   A = blockdiag_k(H_k + diag d_x,k + delta_k I)  (+)  diag(d_x of the six globals)
+ * is symmetric quasi-definite: its inertia is exactly (n, m, 0), the figure IPOPT's regularisation loop is driven by, and nobody had to
+ * factor K'.  (K' is the operator with d_x' = d_x + delta_k on knot k's variables; a periodicity coupling of the horizon ends that the
+ * Hessian pattern has lies outside every block and is NOT covered by this statement.)  The limit: this is a SUFFICIENT correction and a
+ * conservative one, NOT IPOPT's criterion.  IPOPT needs only the Hessian reduced to the null space of J positive definite and adds one
+ * delta to the whole top block; a delta per knot that makes every whole block positive definite can be larger than that needs.
+ * delta_init and kappa have no defaults here; nothing about MINRES's convergence on K' is claimed.  Cost: (tries + 1) whole
+ * factorisations for the slowest knot of a launch; measured: profiles/r17_kkt_ladder.txt (tools/kkt_ladder_probe.py).
+ * HIPNLP_E_INVALID, refused before anything is launched: what hipnlp_kkt_block_factor_device refuses, a null delta_dev or tries_dev,
+ * max_tries outside 0 .. 16, and with max_tries > 0 a delta_init that is not a finite number > 0 or a kappa that is not a finite number
+ * > 1.  HIPNLP_E_UNSUPPORTED as hipnlp_kkt_block_factor_device. */
+int hipnlp_kkt_block_ladder_device(hipnlp_handle* h, const double* hess_values_dev, const double* dx_dev /*or NULL*/, double floor, double delta_init, double kappa,
+                                   int max_tries, double* factor_dev, int32_t* pivots_dev, double* e_dev, double* o_dev, int32_t* inertia_dev, int32_t* status_dev,
+                                   double* delta_dev /*[batch][N]*/, int32_t* tries_dev /*[batch][N]*/, void* stream);
+
 /* Sharded variant (multi-GPU): the handle owns knots [knot_begin, knot_end).  Outputs are
  * shard-local and contiguous so that one RCCL all-gather reassembles them:
  *   grad_shard [batch][shard_grad]  = grad f entries of the shard's knots (+ the 6 global entries on the last shard)

@@ -2,8 +2,9 @@
 """Register / scratch / LDS figures of every kernel in a built libhipnlp.so, read from the code-object metadata of the library
 ITSELF (what the GPU box will load), not from a fresh compile: the .hip_fatbin section holds one clang offload bundle per
 translation unit; its gfx950 entries are ELF code objects whose NT_AMDGPU_METADATA note lists every kernel.
-The kernels of the per-knot block preconditioner (KKT_BLOCK) have a table of their own: kernel_resources() lists every other kernel,
-kernel_resources(table="kkt_block") these three.
+The kernels of the per-knot block preconditioner (KKT_BLOCK) have a table of their own, and so has its inertia-correcting ladder
+(KKT_LADDER): kernel_resources() lists every other kernel, kernel_resources(table="kkt_block") those three, kernel_resources(table=
+"kkt_ladder") that one.
     python tools/kernel_resources.py [path/to/libhipnlp.so]"""
 import os
 import re
@@ -17,6 +18,9 @@ LLVM = os.environ.get("HIPNLP_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 # the table of the block preconditioner of the KKT solve (hipnlp.hip; knot_ldl.h)
 KKT_BLOCK = ("hipnlp_kkt_block_factor_kernel", "hipnlp_kkt_block_apply_kernel", "hipnlp_kkt_minres_block_first_kernel")
+# the table of the per-knot inertia-correcting ladder of that factorisation
+KKT_LADDER = ("hipnlp_kkt_block_ladder_kernel",)
+TABLES = {"kkt_block": KKT_BLOCK, "kkt_ladder": KKT_LADDER}
 
 
 def code_objects(lib_path, tmp):
@@ -43,7 +47,7 @@ def code_objects(lib_path, tmp):
 
 
 def kernel_resources(lib_path=None, table="main"):
-    """{demangled-ish kernel name: {"vgpr", "sgpr", "scratch", "lds", "wg"}} of one table: "main" (every kernel but KKT_BLOCK's) or "kkt_block" (these)"""
+    """{demangled-ish kernel name: {"vgpr", "sgpr", "scratch", "lds", "wg"}} of one table: "kkt_block" (KKT_BLOCK's), "kkt_ladder" (KKT_LADDER's) or "main" (every other kernel)"""
     lib_path = lib_path or os.path.join(ROOT, "hippopt_amd", "lib", "libhipnlp.so")
     res = {}
     with tempfile.TemporaryDirectory(prefix="hipnlp_res_") as tmp:
@@ -65,7 +69,7 @@ def kernel_resources(lib_path=None, table="main"):
                         while args and args[-1] == ("b", "0"):   # (trailing `false` defaults are left out: <0,4> is <0,4,false>)
                             args.pop()
                         short += "<" + ",".join(("true" if v == "1" else "false") if k == "b" else v for k, v in args) + ">"
-                if (short.split("<")[0] in KKT_BLOCK) != (table == "kkt_block"):
+                if next((t for t, names in TABLES.items() if short.split("<")[0] in names), "main") != table:
                     continue
                 res[short] = {"vgpr": num("vgpr_count"), "agpr": int(blk.split()[0]), "sgpr": num("sgpr_count"), "scratch": num("private_segment_fixed_size"),
                               "lds": num("group_segment_fixed_size"), "wg": num("max_flat_workgroup_size")}
@@ -73,7 +77,7 @@ def kernel_resources(lib_path=None, table="main"):
 
 
 if __name__ == "__main__":
-    for table in ("main", "kkt_block"):
+    for table in ("main", "kkt_block", "kkt_ladder"):
         r = kernel_resources(sys.argv[1] if len(sys.argv) > 1 else None, table)
         for k in sorted(r):
             v = r[k]
