@@ -25,6 +25,8 @@
     z = K.solve(b_top, b_bottom, minv=M)                   # ... MINRES with the block top (hipnlp_kkt_minres_block_device)
     P = K.convexify()                                      # per-knot inertia-correcting ladder (hipnlp_kkt_block_ladder_device): P.delta, P.tries, P.quasi_definite
     z = P.values.solve(b_top, b_bottom, minv=P)            # ... MINRES on the convexified operator P.values with the exact inverse of its top blocks
+    Cp = K.condensed_preconditioner()                      # per-knot L |D| L^T of B_k = H_k + dx_k + J_k^T diag(1/dc) J_k (hipnlp_kkt_condensed_factor_device); needs dc
+    z = K.solve(b_top, b_bottom, minv=Cp)                  # ... MINRES with the condensed block top and 1/dc at the bottom; Cp.inertia: see its docstring
 
 The forward pass is hipnlp_eval_device with grad f and jac g left out; the backward pass is the Lagrangian gradient
 sigma grad f + J^T lambda with sigma = df, lambda = dg (zeros for an output whose gradient is None): the Jacobian never reaches memory.
@@ -380,6 +382,48 @@ class KKTValues:
         quasi = quasi & (self.dc > 0.0).all(dim=1) if self.dc is not None else torch.zeros_like(quasi)
         return KKTBlockPreconditioner(convex, factor, pivots, e, o, inertia, status, top, bottom, delta=delta, tries=tries, quasi_definite=quasi)
 
+    def condensed_preconditioner(self, floor=1e-10):
+        """KKTBlockPreconditioner of the CONDENSED blocks, ready for solve(minv=...) and apply(); raises ValueError without dc.  Where
+        dc > 0 the bottom block of K can be eliminated instead of approximated: C = H + diag dx + J^T diag(1 / dc) J, and by Haynsworth
+        In(K) = (0, m, 0) + In(C).  C is block tridiagonal by knot; ONE launch (hipnlp_kkt_condensed_factor_device, one workgroup per knot
+        and trajectory) assembles and factors its diagonal blocks B_k = H_k + diag dx_k + J_k^T diag(1 / dc) J_k from the knot's own column
+        block of jac g and writes the diagonal that goes with them: .bottom = 1 / dc, .top_diagonal = 1 / max(|diag B_k|, floor) and, at
+        the six globals, 1 / max(|dx_g + sum_i J_ig^2 / dc_i|, floor).  (pre.top_diagonal, pre.bottom) alone is a condensed DIAGONAL
+        preconditioner for solve(minv=(top, bottom)).  M^-1 = blockdiag_k(P_k^T L_k^-T |D_k|^-1 L_k^-1 P_k) (+) that diagonal, positive
+        definite whatever the inertia.  .condensed is True; the other attributes are block_preconditioner's, of the blocks B_k.
+        .status [batch, N]: 0 factored; 2 block data not finite, or a dc_i of a row touching the knot's column block that is not a finite
+        number > 0 (that row's .bottom is NaN); such a knot's elements come out of apply as NaN, solve: status 2.
+        WHAT .inertia PROVES: every B_k is a principal submatrix of C, so a B_k with a negative (or zero) eigenvalue proves that K does NOT
+        have IPOPT's inertia (n, m, 0).  All B_k positive definite proves NOTHING about K: C's off-diagonal blocks are not looked at.
+        Measured with the CPU emulation (rtol 1e-8, real N = 4 value runs): 58 iterations against block_preconditioner's 315 (periodic),
+        133 against 456 (stairs); with dx, dc a factor 1e-4 smaller 247 and 340 where block_preconditioner stands at status 1 after 3 000.
+        On the device (profiles/r18_kkt_condensed.txt): the launch is 1.14 x block_preconditioner's factor launch, an iteration costs the
+        same; at 100 x 1 and 100 x 64 (planar) every trajectory converges within 3 000 iterations at both scales (556; 282 - 1 017) where
+        the block preconditioner does not; on the stairs at 200 x 16 nothing converges.  NOT claimed: convergence at other shapes or diagonals; that an interior-point
+        step is cheap with it; any inertia correction (a ladder on B_k is not built); anything about the off-diagonal blocks of C — a
+        block-tridiagonal factorisation would be the exact inverse of C, this is not.  Nothing is synchronised."""
+        torch, nlp = _torch(), self.nlp
+        floor = _checked_floor(floor)
+        if self.dc is None:
+            raise ValueError("condensed_preconditioner: the condensed block eliminates the bottom block, which needs dc > 0 — these values have no dc (with_diagonals)")
+        dev, nbytes = self.hess.device, nlp.engine.kkt_block_bytes()
+        N = (nlp.n - 6) // self.ORDER                                          # knots: n = 189 N + the six globals
+        factor = torch.empty((nlp.batch, N, nbytes[0] // (8 * nlp.batch * N)), dtype=torch.float64, device=dev)
+        pivots = torch.empty((nlp.batch, N, nbytes[1] // (4 * nlp.batch * N)), dtype=torch.int32, device=dev)
+        e = torch.empty((nlp.batch, N, nbytes[2] // (8 * nlp.batch * N)), dtype=torch.float64, device=dev)
+        assert factor.shape[2] == self.ORDER * (self.ORDER + 1) // 2 and pivots.shape[2] == e.shape[2] == self.ORDER
+        o = torch.empty_like(e)
+        inertia = torch.empty((nlp.batch, N, 3), dtype=torch.int32, device=dev)
+        status = torch.empty((nlp.batch, N), dtype=torch.int32, device=dev)
+        top = torch.empty((nlp.batch, nlp.n), dtype=torch.float64, device=dev)
+        bottom = torch.empty((nlp.batch, nlp.m), dtype=torch.float64, device=dev)
+        nlp._on_current_stream(lambda s: nlp.engine.kkt_condensed_factor_device(self.hess.data_ptr(), self.jac.data_ptr(), self.dc.data_ptr(), factor.data_ptr(), pivots.data_ptr(),
+                                                                                e.data_ptr(), o.data_ptr(), inertia.data_ptr(), status.data_ptr(), top.data_ptr(), bottom.data_ptr(),
+                                                                                dx_ptr=self.dx.data_ptr() if self.dx is not None else 0, floor=floor, stream=s))
+        pre = KKTBlockPreconditioner(self, factor, pivots, e, o, inertia, status, top, bottom)
+        pre.condensed = True
+        return pre
+
     def solve(self, rhs_top, rhs_bottom, rtol=1e-8, maxiter=200, minv=None, check_every=16):
         """KKTSolution(top [batch, n], bottom [batch, m], iterations [batch] int32, residual [batch], status [batch] int32) of
         K [top; bottom] = [rhs_top; rhs_bottom] by preconditioned MINRES from a zero start, resident on the device
@@ -446,7 +490,11 @@ class KKTBlockPreconditioner:
     and .bottom [batch, m] (the diagonal preconditioner's).  apply(r_top, r_bottom) is ONE launch (hipnlp_kkt_block_apply_device);
     KKTValues.solve(minv=this) runs MINRES with it.  Tied to the value runs and diagonals it was built from.
     What KKTValues.convexify built has, beside these, .delta [batch, N], .tries [batch, N] int32 and .quasi_definite [batch] bool (None
-    on what block_preconditioner built), and its .values is the CONVEXIFIED operator — the one to solve on with it."""
+    on what block_preconditioner built), and its .values is the CONVEXIFIED operator — the one to solve on with it.
+    What KKTValues.condensed_preconditioner built has .condensed True (False otherwise): its records are those of the condensed blocks
+    B_k = H_k + diag dx_k + J_k^T diag(1 / dc) J_k, .bottom is 1 / dc and .top_diagonal the condensed diagonal, all from one launch."""
+
+    condensed = False   # True on what KKTValues.condensed_preconditioner built
 
     def __init__(self, values, factor, pivots, e, o, inertia, status, top_diagonal, bottom, *, delta=None, tries=None, quasi_definite=None):
         self.nlp, self.values = values.nlp, values

@@ -34,6 +34,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "knot_condense.h"
 #include "knot_hess_layout.h"
 #include "knot_kkt.h"
 #include "knot_kkt_precond.h"
@@ -2098,6 +2099,161 @@ __global__ __launch_bounds__(KLD_WG) void hipnlp_kkt_block_ladder_kernel(KnotLdl
     }
 }
 
+// The CONDENSED block of knot_condense.h: the factor kernel's mapping, triangle and factorisation on B_k = H_k + diag d_x,k +
+// J_k^T diag(1 / d_c) J_k.  The assembly stages, BESIDE the triangle and over the words the factorisation uses later (x0, x1, ipiv, perm,
+// kind: dead until then), the knot's column block of jac g in (column, row) order, the rank of every entry's row, the column directory and
+// s = 1 / d_c of the rows touching the block — 20 152 B, so the workgroup holds 163 792 B of the 163 840 B a workgroup can have.  Every
+// element of the triangle then merges the lists of its two columns (kc_element): the columns dealt to the waves, the lanes along the
+// packed column, as in the trailing update.  No atomics, no exchange between workgroups, every loop bounded by the table sizes.
+// The launch also writes the whole condensed diagonal: minv_bottom by minres_owned's rows, minv_top of the knot's variables from the
+// assembled diagonal, the six globals by the last knot.
+struct KnotCondArgs {
+    KnotLdlArgs f;
+    const KnotCondenseTables* ct;
+    const JprodTables* jt;
+    const double* jvals;          // [batch][nnz]
+    const double* dc;             // [batch][m]
+    double* minv_top;             // [batch][n]
+    double* minv_bottom;          // [batch][m]
+    JacRunDims jd;
+};
+struct alignas(8) KnotCondStage {
+    double v[KC_ENT_CAP];                    // the block's values in (column, row) order
+    double s[KC_ROW_CAP];                    // 1 / d_c of the row of rank q
+    uint16_t rank[KC_ENT_CAP];
+    uint16_t cbeg[KC_COL_WORDS];
+    int32_t bad, pad;
+};
+constexpr int KC_TRIANGLE_BYTES = KL_DOUBLES * int(sizeof(double));
+constexpr int KC_LDS_BYTES = KC_TRIANGLE_BYTES + int(sizeof(KnotCondStage)) > int(sizeof(KnotLdlLds)) ? KC_TRIANGLE_BYTES + int(sizeof(KnotCondStage)) : int(sizeof(KnotLdlLds));
+static_assert(KC_LDS_BYTES <= 160 * 1024 && KC_TRIANGLE_BYTES % 8 == 0 && offsetof(KnotLdlLds, a) == 0, "one workgroup's LDS; the staging behind the triangle");
+static_assert(KC_ROW_CAP <= KLD_WG && KC_COL_WORDS <= KLD_WG && JP_WG <= KLD_WG && JP_V_STRIDE + NXG <= KLD_WG, "one thread per staged row, column word, owned row pair, global");
+
+// The assembly of B_k (+ delta on the diagonal where with_delta: what a ladder on B_k would call) into s.a from staged st; ends behind a
+// barrier.  st.v, st.s, st.rank and st.cbeg are complete and a barrier lies behind them.
+__device__ __forceinline__ void knot_condense_assemble(KnotLdlLds& s, const KnotCondStage& st, const KnotLdlArgs& a, const double* hv, int cnt, int tid, bool with_dx, double dx_c,
+                                                       bool with_delta, double delta) {
+    constexpr int N = KL_N;
+    const int lane = tid & 63, wave = tid >> 6;
+    for (int e = tid; e < cnt; e += KLD_WG) {
+        const int32_t at = a.lt->at[e];
+        if (at >= 0 && at < KL_DOUBLES) s.a[at] = hv[e];
+    }
+    lds_barrier();
+    if (tid < N) { const int p = pl_col(N, tid); s.a[p] = pl_diag_top(s.a[p], with_dx, dx_c, with_delta, delta); }
+    lds_barrier();
+    for (int j = wave; j < N; j += KLD_WAVES) {
+        const int cj = pl_col(N, j) - j;                                      // (i, j) at cj + i
+        const int cb = st.cbeg[j], ce = st.cbeg[j + 1];
+        for (int i = j + lane; i < N; i += 64)
+            s.a[cj + i] = kc_element(s.a[cj + i], int(st.cbeg[i]), int(st.cbeg[i + 1]), cb, ce, [&](int e) { return int(st.rank[e]); }, [&](int e) { return st.v[e]; },
+                                     [&](int q) { return st.s[q]; });
+    }
+    lds_barrier();
+}
+
+__global__ __launch_bounds__(KLD_WG) void hipnlp_kkt_condensed_factor_kernel(KnotCondArgs ca) {
+    __shared__ alignas(16) unsigned char raw[KC_LDS_BYTES];
+    KnotLdlLds& s = *reinterpret_cast<KnotLdlLds*>(raw);
+    KnotCondStage& st = *reinterpret_cast<KnotCondStage*>(raw + KC_TRIANGLE_BYTES);
+    constexpr int N = KL_N;
+    const KnotLdlArgs& a = ca.f;
+    const JacRunDims& jd = ca.jd;
+    const int tid = threadIdx.x, k = blockIdx.x, b = blockIdx.y;
+    const int64_t rec = int64_t(b) * a.N + k;
+    const int v = block_variant(k, a.N), pv = pair_variant(k, a.N);
+    const bool last = k == a.N - 1;
+    const KnotCondenseTables& ct = *ca.ct;
+    const bool with_dx = a.dx != nullptr;
+    const double dx_c = (with_dx && tid < N) ? a.dx[int64_t(b) * a.n + int64_t(NXK) * k + tid] : 0.0;
+    const double* dcb = ca.dc + int64_t(b) * jd.m;
+    const double* jvb = ca.jvals + int64_t(b) * jd.nnz;
+    const double* jv = jvb + jd.block_base(k);
+    const int blen = jd.block_len(k);
+    const int ne = ct.nent[v] < KC_ENT_CAP ? ct.nent[v] : KC_ENT_CAP, nr = ct.nrows[v] < KC_ROW_CAP ? ct.nrows[v] : KC_ROW_CAP;
+    // ---- the condensed diagonal's bottom: minres_owned's rows
+    if (tid < JP_WG) {
+        double* out = ca.minv_bottom + int64_t(b) * jd.m;
+#pragma unroll
+        for (int it = 0; it < JP_ROW_CAP / JP_WG; ++it) {
+            const int32_t ra = ca.jt->row_a[pv][tid + it * JP_WG];
+            if (ra == G_NONE) continue;
+            const int32_t r = ra + ca.jt->row_b[pv][tid + it * JP_WG] * k;
+            if (r >= 0 && r < jd.m) out[r] = kc_scale(dcb[r]);
+        }
+    }
+    // ---- the six globals' top, by the last knot
+    if (last && tid >= JP_V_STRIDE && tid < JP_V_STRIDE + NXG) {
+        const int g = tid - JP_V_STRIDE;
+        double acc = with_dx ? a.dx[int64_t(b) * a.n + int64_t(NXK) * a.N + g] : 0.0;
+        const int gb = ct.gbeg[g], ge = ct.gbeg[g + 1] < JP_GLOB_CAP ? ct.gbeg[g + 1] : JP_GLOB_CAP;
+        for (int e = gb; e < ge; ++e) {
+            const int32_t p = ct.gpos[e], r = ct.grow[e];
+            if (p < 0 || p >= jd.nnz_glob || r < 0 || r >= jd.m) continue;
+            const double aj = jvb[jd.glob_base + p];
+            acc = kc_term(acc, aj, aj, kc_scale(dcb[r]));
+        }
+        ca.minv_top[int64_t(b) * a.n + int64_t(NXK) * a.N + g] = kc_top(acc, a.floor);
+    }
+    // ---- the staging beside the triangle
+    for (int e = tid; e < KL_DOUBLES; e += KLD_WG) s.a[e] = 0.0;
+    if (tid == 0) { st.bad = 0; st.pad = 0; }
+    for (int e = tid; e < KC_ENT_CAP; e += KLD_WG) {
+        const int p = ct.pos[v][e], q = ct.rank[v][e];
+        st.v[e] = (e < ne && p < blen) ? jv[p] : 0.0;
+        st.rank[e] = uint16_t(q < KC_ROW_CAP ? q : KC_ROW_CAP - 1);
+    }
+    if (tid < KC_COL_WORDS) { const int c = ct.cbeg[v][tid]; st.cbeg[tid] = uint16_t(c < ne ? c : ne); }
+    bool bad_here = false;
+    if (tid < KC_ROW_CAP) {
+        double sv = 0.0;
+        if (tid < nr) {
+            const int32_t r = ct.row_a[v][tid] + ct.row_b[v][tid] * k;
+            sv = (r >= 0 && r < jd.m) ? kc_scale(dcb[r]) : pl_nan();
+            bad_here = !kc_scale_good(sv);
+        }
+        st.s[tid] = sv;
+    }
+    lds_barrier();
+    if (bad_here) st.bad = 1;
+    // ---- assembly of B_k
+    const double* hv = a.hvals + int64_t(b) * a.hd.nnz_h + int64_t(a.hd.nnz_knot) * k;
+    const int cnt = a.hd.nnz_knot < KL_ENT_CAP ? a.hd.nnz_knot : KL_ENT_CAP;
+    knot_condense_assemble(s, st, a, hv, cnt, tid, with_dx, dx_c, false, 0.0);
+    const double bdiag = tid < N ? s.a[pl_col(N, tid)] : 0.0;
+    const bool dc_bad = st.bad != 0;
+    lds_barrier();                                                            // the staging is dead from here: the factorisation's words lie over it
+    // ---- factorisation
+    int pos = 0, neg = 0, zero = 0, status = KL_NONFINITE;
+    if (!dc_bad) status = knot_ldl_factor<2>(s, tid, pos, neg, zero);
+    lds_barrier();
+    const bool good = status == KL_OK;
+    // ---- the stores: every word of the record, whatever the status
+    double* f = a.factor + rec * int64_t(KL_DOUBLES);
+    for (int e = tid; e < KL_DOUBLES; e += KLD_WG) f[e] = good ? s.a[e] : pl_nan();
+    if (tid < N) {
+        const int64_t i = rec * int64_t(N) + tid;
+        double ev = pl_nan(), ov = pl_nan();
+        int32_t word = kl_word(tid + 1, tid, PL_ONE);
+        if (good) {
+            const int kind = s.kind[tid], ci = pl_col(N, tid);
+            word = kl_word(s.ipiv[tid], s.perm[tid], kind);
+            ov = 0.0;
+            if (kind == PL_ONE) ev = kl_floored_inverse(s.a[ci], a.floor);
+            else if (kind == PL_FIRST) { const KlAbsInv2 q = kl_abs_inverse2(s.a[ci], s.a[ci + 1], s.a[pl_col(N, tid + 1)], a.floor); ev = q.e0; ov = q.o; }
+            else { const int cp = pl_col(N, tid - 1); ev = kl_abs_inverse2(s.a[cp], s.a[cp + 1], s.a[ci], a.floor).e1; }
+        }
+        a.pivots[i] = word;
+        a.e[i] = ev;
+        a.o[i] = ov;
+        ca.minv_top[int64_t(b) * a.n + int64_t(NXK) * k + tid] = kc_top(bdiag, a.floor);
+    }
+    if (tid == 0) {
+        a.inertia[rec * 3 + 0] = good ? pos : 0; a.inertia[rec * 3 + 1] = good ? neg : 0; a.inertia[rec * 3 + 2] = good ? zero : 0;
+        a.status[rec] = status;
+    }
+}
+
 // One knot's  z = P^T L^-T |D|^-1 L^-1 P r  by ONE wave (knot_ldl.h APPLY): lane l holds the elements l, l + 64, l + 128 in three named
 // registers.  f, words, e, o: of this knot's record.  src(j): r_j, dst(j, v): z_j = v, j an index of the knot's 189.
 constexpr int KLA_AHEAD = 4;   // columns / rows of L requested ahead of the one in use
@@ -2578,6 +2734,7 @@ struct hipnlp_handle {
     int32_t* h_minres_status = nullptr;  // pinned [batch]: the statuses a check_every > 0 solve looks at
     SaddleDiagTables* d_dt = nullptr;    // hipnlp_kkt_diag_precond_device: the diagonal positions of the Hessian block, uploaded at the first call
     KnotLdlTables* d_klt = nullptr;      // hipnlp_kkt_block_factor_device: the packed places of a knot block's entries (knot_ldl.h), uploaded at the first call
+    KnotCondenseTables* d_kct = nullptr; // hipnlp_kkt_condensed_factor_device: the column directory of a knot's block of jac g (knot_condense.h), uploaded at the first call
     std::string err;
 };
 
@@ -2632,7 +2789,7 @@ static void free_all(hipnlp_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->dev);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void* dptrs[] = {h->d_tb, h->d_ctpl, h->d_ctpl_of_b, h->d_healed, h->d_x, h->d_pk, h->d_cost_knot, h->d_gp, h->d_cost_pub, h->d_out, h->d_ht, h->d_sigma, h->d_hess, h->d_hflag, h->d_htrash, h->d_lt, h->d_vt, h->d_jt, h->d_jtt, h->d_jdot, h->d_minres, h->d_dt, h->d_klt};
+    void* dptrs[] = {h->d_tb, h->d_ctpl, h->d_ctpl_of_b, h->d_healed, h->d_x, h->d_pk, h->d_cost_knot, h->d_gp, h->d_cost_pub, h->d_out, h->d_ht, h->d_sigma, h->d_hess, h->d_hflag, h->d_htrash, h->d_lt, h->d_vt, h->d_jt, h->d_jtt, h->d_jdot, h->d_minres, h->d_dt, h->d_klt, h->d_kct};
     for (void* q : dptrs) if (q) (void)hipFree(q);
     void* hptrs[] = {h->h_x, h->h_out, h->h_hess, h->h_hflag, h->h_sl, h->h_minres_status};
     for (void* q : hptrs) if (q) (void)hipHostFree(q);
@@ -4107,6 +4264,34 @@ int hipnlp_kkt_block_ladder_device(hipnlp_handle* h, const double* hess_values_d
     a.f.inertia = inertia_dev; a.f.status = status_dev; a.f.floor = floor; a.f.N = h->L.N; a.f.n = h->L.n; a.f.hd = hess_run_dims(h);
     a.delta_init = delta_init; a.kappa = kappa; a.delta = delta_dev; a.tries = tries_dev; a.max_tries = max_tries;
     hipLaunchKernelGGL(hipnlp_kkt_block_ladder_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(KLD_WG), 0, stream ? hipStream_t(stream) : h->stream, a);
+    HIP_TRY(h, hipGetLastError());
+    return HIPNLP_OK;
+}
+int hipnlp_kkt_condensed_factor_device(hipnlp_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev, const double* dc_dev, double floor,
+                                       double* factor_dev, int32_t* pivots_dev, double* e_dev, double* o_dev, int32_t* inertia_dev, int32_t* status_dev, double* minv_top_dev,
+                                       double* minv_bottom_dev, void* stream) {
+    if (!h) return HIPNLP_E_INVALID;
+    if (const char* e = kc_factor_call_error(hess_values_dev, jac_values_dev, dc_dev, floor, factor_dev, pivots_dev, e_dev, o_dev, inertia_dev, status_dev, minv_top_dev,
+                                             minv_bottom_dev)) {
+        h->err = std::string("hipnlp_kkt_condensed_factor_device: ") + e;
+        return HIPNLP_E_INVALID;
+    }
+    if (const int rc = kkt_block_prepare(h, "hipnlp_kkt_condensed_factor_device")) return rc;
+    if (const int rc = kkt_block_table(h)) return rc;
+    if (!h->d_kct) {
+        KnotCondenseTables* t = new KnotCondenseTables();
+        std::string why;
+        if (!kc_build_tables(h->L, *t, why)) { delete t; h->err = "hipnlp_kkt_condensed_factor_device: " + why; return HIPNLP_E_UNSUPPORTED; }
+        const int rc = upload_table(h, reinterpret_cast<void**>(&h->d_kct), t, sizeof(KnotCondenseTables), "condensation tables");
+        delete t;
+        if (rc != HIPNLP_OK) return rc;
+    }
+    HIP_TRY(h, hipSetDevice(h->dev));
+    KnotCondArgs a;
+    a.f.lt = h->d_klt; a.f.hvals = hess_values_dev; a.f.dx = dx_dev; a.f.factor = factor_dev; a.f.pivots = pivots_dev; a.f.e = e_dev; a.f.o = o_dev;
+    a.f.inertia = inertia_dev; a.f.status = status_dev; a.f.floor = floor; a.f.N = h->L.N; a.f.n = h->L.n; a.f.hd = hess_run_dims(h);
+    a.ct = h->d_kct; a.jt = h->d_jt; a.jvals = jac_values_dev; a.dc = dc_dev; a.minv_top = minv_top_dev; a.minv_bottom = minv_bottom_dev; a.jd = jac_run_dims(h);
+    hipLaunchKernelGGL(hipnlp_kkt_condensed_factor_kernel, dim3(unsigned(h->nk), unsigned(h->batch)), dim3(KLD_WG), 0, stream ? hipStream_t(stream) : h->stream, a);
     HIP_TRY(h, hipGetLastError());
     return HIPNLP_OK;
 }

@@ -31,7 +31,7 @@ EXPORTS = [
     "hipnlp_jac_times_device", "hipnlp_jac_transpose_times_device", "hipnlp_kkt_times_device", "hipnlp_kkt_minres_device", "hipnlp_kkt_minres_reserve",
     "hipnlp_kkt_diag_precond_device",
     "hipnlp_kkt_block_bytes", "hipnlp_kkt_block_factor_device", "hipnlp_kkt_block_apply_device", "hipnlp_kkt_minres_block_device",
-    "hipnlp_kkt_block_ladder_device",
+    "hipnlp_kkt_block_ladder_device", "hipnlp_kkt_condensed_factor_device",
     "hipnlp_eval_pinned", "hipnlp_set_prefetch", "hipnlp_set_early_outputs", "hipnlp_set_host_timing", "hipnlp_host_register", "hipnlp_host_unregister",
     "hipnlp_multi_create", "hipnlp_multi_plan", "hipnlp_multi_info", "hipnlp_multi_breakdown", "hipnlp_multi_set_threads",
     "hipnlp_host_breakdown", "hipnlp_set_auto_register", "hipnlp_host_stats", "hipnlp_set_constant_jacobian", "hipnlp_forget_jac_destination", "hipnlp_jac_constant_mask", "hipnlp_host_release_auto_ranges",
@@ -247,6 +247,8 @@ def load_library(path=None):
         lib.hipnlp_kkt_minres_block_device.argtypes = [vp] * 15 + [C.c_double, C.c_int, C.c_int] + [vp] * 4
     if hasattr(lib, "hipnlp_kkt_block_ladder_device"):
         lib.hipnlp_kkt_block_ladder_device.argtypes = [vp] * 3 + [C.c_double] * 3 + [C.c_int] + [vp] * 9
+    if hasattr(lib, "hipnlp_kkt_condensed_factor_device"):
+        lib.hipnlp_kkt_condensed_factor_device.argtypes = [vp] * 5 + [C.c_double] + [vp] * 9
     _libs[path] = lib
     return lib
 
@@ -702,6 +704,18 @@ class HipNlp:
         self._check(self.lib.hipnlp_kkt_block_ladder_device(self.h, vp(hess_values_ptr or None), vp(dx_ptr or None), float(floor), float(delta_init), float(kappa), int(max_tries),
                                                             vp(factor_ptr or None), vp(pivots_ptr or None), vp(e_ptr or None), vp(o_ptr or None), vp(inertia_ptr or None),
                                                             vp(status_ptr or None), vp(delta_ptr or None), vp(tries_ptr or None), vp(stream or None)))
+
+    def kkt_condensed_factor_device(self, hess_values_ptr, jac_values_ptr, dc_ptr, factor_ptr, pivots_ptr, e_ptr, o_ptr, inertia_ptr, status_ptr, minv_top_ptr, minv_bottom_ptr,
+                                    dx_ptr=0, floor=1e-10, stream=0):
+        """kkt_block_factor_device on the CONDENSED blocks B_k = H_k + diag dx_k + J_k^T diag(1 / dc) J_k, in ONE launch
+        (hipnlp_kkt_condensed_factor_device): the six arrays in kkt_block_factor_device's format, plus ALL of minv_top [batch][n] and
+        minv_bottom [batch][m] (1 / max(|diag B_k|, floor), the six globals' condensed diagonal, 1 / dc).  dc is required.  Status 2 also
+        for a knot whose column block is touched by a row with a dc that is not a finite number > 0; asynchronous on `stream`"""
+        vp = C.c_void_p
+        self._check(self.lib.hipnlp_kkt_condensed_factor_device(self.h, vp(hess_values_ptr or None), vp(jac_values_ptr or None), vp(dx_ptr or None), vp(dc_ptr or None),
+                                                                float(floor), vp(factor_ptr or None), vp(pivots_ptr or None), vp(e_ptr or None), vp(o_ptr or None),
+                                                                vp(inertia_ptr or None), vp(status_ptr or None), vp(minv_top_ptr or None), vp(minv_bottom_ptr or None),
+                                                                vp(stream or None)))
 
     def kkt_block_apply_device(self, factor_ptr, pivots_ptr, e_ptr, o_ptr, minv_top_ptr, minv_bottom_ptr, r_top_ptr, r_bottom_ptr, z_top_ptr, z_bottom_ptr, stream=0):
         """[z_top; z_bottom] = M^-1 [r_top; r_bottom] in ONE launch (hipnlp_kkt_block_apply_device): the knot blocks from the stored

@@ -661,6 +661,32 @@ int hipnlp_kkt_block_ladder_device(hipnlp_handle* h, const double* hess_values_d
                                    int max_tries, double* factor_dev, int32_t* pivots_dev, double* e_dev, double* o_dev, int32_t* inertia_dev, int32_t* status_dev,
                                    double* delta_dev /*[batch][N]*/, int32_t* tries_dev /*[batch][N]*/, void* stream);
 
+/* The CONDENSED block factorisation (knot_condense.h), ONE launch on hipnlp_kkt_block_factor_device's mapping: where d_c > 0 the bottom
+ * block of K is eliminated instead of approximated,
+ *     C = H + diag d_x + J^T diag(1 / d_c) J,      In(K) = (0, m, 0) + In(C)   (Haynsworth),
+ * and every knot factors the diagonal block of C it can form alone, B_k = H_k + diag d_x,k + J_k^T diag(1 / d_c) J_k, J_k the knot's
+ * column block of the stored jac run.  The six stored arrays have hipnlp_kkt_block_factor_device's format and status convention, so
+ * hipnlp_kkt_block_apply_device and hipnlp_kkt_minres_block_device take them as they are.  Assembly: that factorisation's, then per
+ * element (r, c) one acc = fma(a_ir, a_ic * s_i, acc), s_i = 1 / d_c,i correctly rounded, for every row i of g with an entry in both
+ * columns, in ascending global row: one writer and one chain per element, no atomics, the same bits in every launch, at every batch
+ * position and in both orders of jac g.
+ * The launch also writes ALL of minv_top_dev [batch][n] and minv_bottom_dev [batch][m] — a condensed DIAGONAL preconditioner on their own
+ * (hipnlp_kkt_minres_device) and what the block apply reads for the six globals and the bottom:
+ *     minv_bottom_i = 1 / d_c,i;   minv_top_j = 1 / max(|B_k,jj|, floor);   six globals: 1 / max(|d_x,g + sum_i J_ig^2 / d_c,i|, floor).
+ * status_dev: 0 factored; 2 the knot's block data is not finite, OR a d_c,i of a row of g touching the knot's column block is not a
+ * finite number > 0: NaN in every word of its factor, e and o, inertia (0, 0, 0); minv_bottom_i of such a row is NaN.
+ * What inertia_dev proves: every B_k is a principal submatrix of C, so a B_k with a negative or zero eigenvalue proves that K does NOT
+ * have the inertia (n, m, 0).  All B_k positive definite proves nothing about K: the off-diagonal blocks of C are not looked at.  Nothing
+ * is retried or regularised; a periodicity coupling of the Hessian pattern stays outside every block.
+ * HIPNLP_E_INVALID, refused before anything is launched: a null dc_dev or jac_values_dev, and what hipnlp_kkt_block_factor_device refuses,
+ * a null minv_top_dev or minv_bottom_dev.  HIPNLP_E_UNSUPPORTED as hipnlp_kkt_block_factor_device (multi-device and shard handles
+ * included), and a layout whose column block has more than 1 620 entries or is touched by more than 439 rows.
+ * Measured: 1.14 x hipnlp_kkt_block_factor_device's launch at 100 x 1, 100 x 64 and stairs 200 x 16 (profiles/r18_kkt_condensed.txt,
+ * tools/kkt_condensed_probe.py). */
+int hipnlp_kkt_condensed_factor_device(hipnlp_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev /*or NULL*/,
+                                       const double* dc_dev /*required*/, double floor, double* factor_dev, int32_t* pivots_dev, double* e_dev, double* o_dev,
+                                       int32_t* inertia_dev, int32_t* status_dev, double* minv_top_dev /*[batch][n]*/, double* minv_bottom_dev /*[batch][m]*/, void* stream);
+
 /* Sharded variant (multi-GPU): the handle owns knots [knot_begin, knot_end).  Outputs are
  * shard-local and contiguous so that one RCCL all-gather reassembles them:
  *   grad_shard [batch][shard_grad]  = grad f entries of the shard's knots (+ the 6 global entries on the last shard)

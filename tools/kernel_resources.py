@@ -2,9 +2,9 @@
 """Register / scratch / LDS figures of every kernel in a built libhipnlp.so, read from the code-object metadata of the library
 ITSELF (what the GPU box will load), not from a fresh compile: the .hip_fatbin section holds one clang offload bundle per
 translation unit; its gfx950 entries are ELF code objects whose NT_AMDGPU_METADATA note lists every kernel.
-The kernels of the per-knot block preconditioner (KKT_BLOCK) have a table of their own, and so has its inertia-correcting ladder
-(KKT_LADDER): kernel_resources() lists every other kernel, kernel_resources(table="kkt_block") those three, kernel_resources(table=
-"kkt_ladder") that one.
+The kernels of the per-knot block preconditioner (KKT_BLOCK) have a table of their own, and so have its inertia-correcting ladder
+(KKT_LADDER) and the condensed block factorisation (KKT_CONDENSED): kernel_resources() lists every other kernel,
+kernel_resources(table="kkt_block") those three, kernel_resources(table="kkt_ladder") and kernel_resources(table="kkt_condensed") that one.
     python tools/kernel_resources.py [path/to/libhipnlp.so]"""
 import os
 import re
@@ -20,7 +20,9 @@ MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 KKT_BLOCK = ("hipnlp_kkt_block_factor_kernel", "hipnlp_kkt_block_apply_kernel", "hipnlp_kkt_minres_block_first_kernel")
 # the table of the per-knot inertia-correcting ladder of that factorisation
 KKT_LADDER = ("hipnlp_kkt_block_ladder_kernel",)
-TABLES = {"kkt_block": KKT_BLOCK, "kkt_ladder": KKT_LADDER}
+# the table of the condensed block factorisation (knot_condense.h)
+KKT_CONDENSED = ("hipnlp_kkt_condensed_factor_kernel",)
+TABLES = {"kkt_block": KKT_BLOCK, "kkt_ladder": KKT_LADDER, "kkt_condensed": KKT_CONDENSED}
 
 
 def code_objects(lib_path, tmp):
@@ -47,7 +49,7 @@ def code_objects(lib_path, tmp):
 
 
 def kernel_resources(lib_path=None, table="main"):
-    """{demangled-ish kernel name: {"vgpr", "sgpr", "scratch", "lds", "wg"}} of one table: "kkt_block" (KKT_BLOCK's), "kkt_ladder" (KKT_LADDER's) or "main" (every other kernel)"""
+    """{demangled-ish kernel name: {"vgpr", "sgpr", "scratch", "lds", "wg"}} of one table: "kkt_block" (KKT_BLOCK's), "kkt_ladder" (KKT_LADDER's), "kkt_condensed" (KKT_CONDENSED's) or "main" (every other kernel)"""
     lib_path = lib_path or os.path.join(ROOT, "hippopt_amd", "lib", "libhipnlp.so")
     res = {}
     with tempfile.TemporaryDirectory(prefix="hipnlp_res_") as tmp:
@@ -77,7 +79,7 @@ def kernel_resources(lib_path=None, table="main"):
 
 
 if __name__ == "__main__":
-    for table in ("main", "kkt_block", "kkt_ladder"):
+    for table in ("main", "kkt_block", "kkt_ladder", "kkt_condensed"):
         r = kernel_resources(sys.argv[1] if len(sys.argv) > 1 else None, table)
         for k in sorted(r):
             v = r[k]
