@@ -60,7 +60,15 @@ The static pose finder, a batch of B independent poses, has the same interface a
 A pose is one workgroup, which holds all of jac g and of the Hessian in LDS: the derivatives of the Lagrangian gradient with respect to
 sigma and lam, grad f . w and J w, are one launch too, so a double backward through any loss in f and g — (f ** 2).sum() + (g ** 2).sum()
 — runs: H w from one launch when x needs it, grad f . w and J w from one launch when sigma or lam needs it.  Nothing raises.
-torch is imported when first needed."""
+
+Graph capture (torch.cuda.graph; the table is DESIGN.md "Graph capture", the proof tests/test_gpu_graph_replay.py).  Every method's
+docstring says which of two classes it is in.  REPLAYABLE: everything reaches the kernels through pointers and by-value arguments that
+no replay invalidates; the method must have run once eagerly on the handle (the engine uploads tables and allocates workspaces at first
+use, and a kernel's code is loaded at its first launch — neither may happen in a capture), else it raises RuntimeError before anything
+is enqueued.  NOT REPLAYABLE: raises RuntimeError while the current stream is capturing, before anything is enqueued or allocated —
+above all KinodynamicNLP.__call__: the cost reducer of hipnlp_eval_device accepts a knot's partial by the launch number, which a
+captured launch bakes in, so a replay could return the previous x's f.  A warmed replayable method pays one set lookup and asks torch
+nothing.  torch is imported when first needed."""
 import collections
 import numbers
 
@@ -72,10 +80,67 @@ _FUNCTION = None
 _LGRAD_FUNCTION = None
 _POSE_LGRAD_FUNCTION = None
 
+# why no backward pass is captured: nothing here proves it.  What the guard COVERS: autograd runs a backward node on the stream of its
+# forward pass, so the query sees a capture only where the forward pass ran on the capturing stream.  A forward pass on another stream is
+# left to torch's and the runtime's own capture errors (the engine would join a stream that is not capturing to one that is).
+_NO_BACKWARD = ("no test replays a backward pass that autograd's engine enqueued (its own stream bookkeeping between the forward and the backward "
+                "pass is not this library's), and a method is called replayable only where a replay test passes")
+# why no launch that evaluates the model at x is captured (but hipnlp_eval_device, which has reasons of its own below)
+_NO_REFERENCE = ("not proven — the launch evaluates the model at x, no CPU reference gives the bits of such a kernel, so the replay test (replays against "
+                 "the eager bits AND an independent bitwise reference) cannot be run for it, and a method is called replayable only where that test passes")
+_STORED = "Evaluate outside the capture and capture what runs on stored value runs (the products, the preconditioners, solve)"
+# why hipnlp_eval_device is not captured: its launch number, and what the handle remembers about jac destinations
+_EVAL_SEQ = ("the cost reducer of hipnlp_eval_device accepts a knot's partial by the launch number, which a captured launch bakes in, so a replay "
+             "can return the previous x's f")
+_EVAL_JAC = ("hipnlp_eval_device always runs its cost reducer on a captured launch number, and it stores only the varying entries of jac g into a "
+             "destination the handle remembers as filled with the constant ones — a table a replay cannot consult — from a template that set_params "
+             "frees")
+
 
 def _torch():
     import torch
     return torch
+
+
+# ---- graph capture: the two guards (module docstring; DESIGN.md "Graph capture") -----------------------------------------------------------
+def _capturing():
+    """is torch's current stream capturing?  A process that never initialised the device captures nothing (and must not be made to
+    initialise it by this question).  torch itself, not _torch(): the tests of the argument checks stand a bare namespace in for
+    _torch(), and the import is a dictionary lookup once torch is loaded."""
+    import torch
+    return torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
+
+
+def _refuse(method, why, remedy):
+    """a method that is NOT replayable: RuntimeError while the current stream is capturing, before anything is enqueued or allocated"""
+    if _capturing():
+        raise RuntimeError("%s cannot be captured into a graph (torch.cuda.graph): %s.  %s." % (method, why, remedy))
+
+
+def _warm_kinds(nlp):
+    """the launch kinds that have run eagerly on nlp's engine handle (the tables and workspaces are the handle's)"""
+    warm = getattr(nlp, "_warm", None)
+    if warm is None or warm[0] is not nlp.engine:
+        warm = nlp._warm = (nlp.engine, set())
+    return warm[1]
+
+
+def _enter(nlp, method, *kinds):
+    """a REPLAYABLE method about to launch `kinds`: the kinds that have not run eagerly on this handle yet — RuntimeError if there are any
+    while the current stream is capturing.  Warmed: set lookups, no torch query."""
+    warm = _warm_kinds(nlp)
+    cold = tuple(k for k in kinds if k not in warm)
+    if cold and _capturing():
+        raise RuntimeError("%s: first use on this handle (%s) while the stream is capturing — at its first call the engine uploads its tables and allocates its "
+                           "workspace, and the kernel's code is loaded, which a capture forbids.  Run %s once outside the capture; after that it is "
+                           "replayable." % (method, ", ".join(k if isinstance(k, str) else " ".join(w for w in k if w) for k in cold), method))
+    return cold
+
+
+def _warmed(nlp, cold):
+    """the launches of _enter's return value have been enqueued eagerly"""
+    if cold:
+        _warm_kinds(nlp).update(cold)
 
 
 def _function():
@@ -87,6 +152,7 @@ def _function():
         class NLPFunction(torch.autograd.Function):
             @staticmethod
             def forward(ctx, x, nlp):
+                nlp._enter_forward()
                 f = torch.empty(nlp.batch, dtype=torch.float64, device=x.device)
                 g = torch.empty(nlp.batch, nlp.m, dtype=torch.float64, device=x.device)
                 nlp._forward(x, f, g)
@@ -98,6 +164,7 @@ def _function():
             def backward(ctx, df, dg):
                 (x,) = ctx.saved_tensors
                 nlp = ctx.nlp
+                _refuse("the backward pass of nlp(x)", _NO_BACKWARD, "Run the backward pass outside the capture")
                 sigma = df.to(torch.float64).contiguous() if df is not None else torch.zeros(nlp.batch, dtype=torch.float64, device=x.device)
                 lam = dg.to(torch.float64).contiguous() if dg is not None else torch.zeros(nlp.batch, nlp.m, dtype=torch.float64, device=x.device)
                 if torch.is_grad_enabled():   # (create_graph=True: the same launch, recorded, so that it can be differentiated in x)
@@ -126,6 +193,7 @@ def _lgrad_function():
             @once_differentiable
             def backward(ctx, w):
                 x, sigma, lam = ctx.saved_tensors
+                _refuse("the double backward pass of nlp(x)", _NO_BACKWARD, "Run it outside the capture")
                 if ctx.nlp.jacobian_products:   # (opt-in: grad f . w and J w from a stored value run — evaluate, then multiply)
                     w = w.to(torch.float64).contiguous()
                     gx = ctx.nlp._launch_hvp(x, sigma, lam, w) if ctx.needs_input_grad[0] else None
@@ -166,6 +234,7 @@ def _pose_lgrad_function():
             def backward(ctx, w):
                 x, sigma, lam = ctx.saved_tensors
                 nlp = ctx.nlp
+                _refuse("the double backward pass of nlp(x)", _NO_BACKWARD, "Run it outside the capture")
                 w = w.to(torch.float64).contiguous()
                 gx = nlp._launch_hvp(x, sigma, lam, w) if ctx.needs_input_grad[0] else None
                 gs = gl = None
@@ -186,10 +255,13 @@ class HessianValues:
         self.nlp, self.values = nlp, values
 
     def matvec(self, v):
+        """H v [batch, n] (hipnlp_hess_times_device), one launch.  Graph capture: replayable after one eager call on the handle."""
         nlp = self.nlp
         nlp._check("v", v, (nlp.batch, nlp.n))
+        cold = _enter(nlp, "HessianValues.matvec", "hess_times")
         out = _torch().empty_like(v, memory_format=_torch().contiguous_format)
         nlp._on_current_stream(lambda s: nlp.engine.hess_times_device(self.values.data_ptr(), v.data_ptr(), out.data_ptr(), stream=s))
+        _warmed(nlp, cold)
         return out
 
 
@@ -202,36 +274,44 @@ class JacobianValues:
         self.nlp, self.grad, self.values = nlp, grad, values
 
     def matvec(self, v):
-        """J v [batch, m] (hipnlp_jac_times_device)"""
+        """J v [batch, m] (hipnlp_jac_times_device).  Graph capture: replayable after one eager call on the handle."""
         self.nlp._check("v", v, (self.nlp.batch, self.nlp.n))
         return self._launch(v, False, True)[1]
 
     def grad_dot(self, v):
-        """grad f . v [batch]"""
+        """grad f . v [batch].  Graph capture: replayable after one eager call on the handle.  (The dot needs a buffer of the handle's that matvec
+        alone does not allocate: warm grad_dot or jvp themselves.)"""
         self.nlp._check("v", v, (self.nlp.batch, self.nlp.n))
         return self._launch(v, True, False)[0]
 
     def jvp(self, v):
-        """(grad f . v [batch], J v [batch, m]) in one launch"""
+        """(grad f . v [batch], J v [batch, m]) in one launch.  Graph capture: replayable after one eager call on the handle.  (The dot needs a
+        buffer of the handle's that matvec alone does not allocate: a warmed matvec does not warm jvp.)"""
         self.nlp._check("v", v, (self.nlp.batch, self.nlp.n))
         return self._launch(v, True, True)
 
     def rmatvec(self, sigma, lam):
-        """sigma grad f + J^T lam [batch, n] (hipnlp_jac_transpose_times_device): sigma a number or a [batch] tensor, lam [batch, m]"""
+        """sigma grad f + J^T lam [batch, n] (hipnlp_jac_transpose_times_device): sigma a number or a [batch] tensor, lam [batch, m].
+        Graph capture: replayable after one eager call on the handle (a number for sigma is baked into the graph: pass a tensor)."""
         nlp = self.nlp
+        cold = _enter(nlp, "JacobianValues.rmatvec", "jac_transpose_times")
         sigma = nlp._sigma(sigma)
         nlp._check("lam", lam, (nlp.batch, nlp.m))
         out = _torch().empty_like(self.grad, memory_format=_torch().contiguous_format)
         nlp._on_current_stream(lambda s: nlp.engine.jac_transpose_times_device(self.values.data_ptr(), lam.data_ptr(), out.data_ptr(), grad_values_ptr=self.grad.data_ptr(),
                                                                                obj_factor_ptr=sigma.data_ptr(), stream=s))
+        _warmed(nlp, cold)
         return out
 
     def _launch(self, v, want_dot, want_jv):
         torch, nlp = _torch(), self.nlp
+        # (the kinds differ where the engine's first-use allocation does: the dot's partials are allocated the first time a dot is asked for)
+        cold = _enter(nlp, "JacobianValues.%s" % ("jvp" if want_dot and want_jv else "grad_dot" if want_dot else "matvec"), ("jac_times", "dot" if want_dot else "", "jv" if want_jv else ""))
         dot = torch.empty(nlp.batch, dtype=torch.float64, device=v.device) if want_dot else None
         jv = torch.empty(nlp.batch, nlp.m, dtype=torch.float64, device=v.device) if want_jv else None
         nlp._on_current_stream(lambda s: nlp.engine.jac_times_device(self.values.data_ptr(), v.data_ptr(), jv.data_ptr() if want_jv else 0, dot.data_ptr() if want_dot else 0,
                                                                      grad_values_ptr=self.grad.data_ptr(), stream=s))
+        _warmed(nlp, cold)
         return dot, jv
 
 
@@ -253,7 +333,9 @@ class KKTValues:
         self.nlp = nlp
         self.hess = hessian_values.values if isinstance(hessian_values, HessianValues) else hessian_values
         self.jac = jacobian_values.values if isinstance(jacobian_values, JacobianValues) else jacobian_values
+        cold = _enter(nlp, "KKTValues(...)", "hess_nnz")   # (the engine builds its Hessian tables when first asked for the pattern's size)
         nlp._check("hessian values", self.hess, (nlp.batch, nlp.engine.hess_nnz()))
+        _warmed(nlp, cold)
         nlp._check("jacobian values", self.jac, (nlp.batch, nlp.engine.nnz))
         if dx is not None:
             nlp._check("dx", dx, (nlp.batch, nlp.n))
@@ -266,15 +348,18 @@ class KKTValues:
         return KKTValues(self.nlp, self.hess, self.jac, dx, dc)
 
     def matvec(self, v, w):
-        """(top [batch, n], bottom [batch, m]) = K [v; w], v [batch, n], w [batch, m]; one launch"""
+        """(top [batch, n], bottom [batch, m]) = K [v; w], v [batch, n], w [batch, m]; one launch.  Graph capture: replayable after one
+        eager call on the handle."""
         torch, nlp = _torch(), self.nlp
         nlp._check("v", v, (nlp.batch, nlp.n))
         nlp._check("w", w, (nlp.batch, nlp.m))
+        cold = _enter(nlp, "KKTValues.matvec", "kkt_times")
         top = torch.empty_like(v, memory_format=torch.contiguous_format)
         bottom = torch.empty_like(w, memory_format=torch.contiguous_format)
         nlp._on_current_stream(lambda s: nlp.engine.kkt_times_device(self.hess.data_ptr(), self.jac.data_ptr(), v.data_ptr(), w.data_ptr(), top.data_ptr(), bottom.data_ptr(),
                                                                      dx_ptr=self.dx.data_ptr() if self.dx is not None else 0,
                                                                      dc_ptr=self.dc.data_ptr() if self.dc is not None else 0, stream=s))
+        _warmed(nlp, cold)
         return top, bottom
 
     def diagonal_preconditioner(self, floor=1e-10):
@@ -283,20 +368,23 @@ class KKTValues:
         this operator's own value runs and diagonals — K.with_diagonals(dx, dc).diagonal_preconditioner() is the one that matches other
         diagonals.  The absolute value keeps M positive definite where H + diag dx is not.  floor > 0 keeps the reciprocals finite; its
         default is a guess nobody has tuned.  A NaN or an infinity in the value runs or diagonals comes out as NaN (solve: status 2).
-        What it was measured to do: solve's docstring."""
+        What it was measured to do: solve's docstring.  Graph capture: replayable after one eager call on the handle."""
         torch, nlp = _torch(), self.nlp
         if not (isinstance(floor, numbers.Real) and not isinstance(floor, bool) and 0.0 < floor < float("inf")):
             raise ValueError("floor: a finite real number > 0, not %r" % (floor,))
+        cold = _enter(nlp, "KKTValues.diagonal_preconditioner", "kkt_diag_precond")
         top = torch.empty((nlp.batch, nlp.n), dtype=torch.float64, device=self.hess.device)
         bottom = torch.empty((nlp.batch, nlp.m), dtype=torch.float64, device=self.hess.device)
         nlp._on_current_stream(lambda s: nlp.engine.kkt_diag_precond_device(self.hess.data_ptr(), self.jac.data_ptr(), top.data_ptr(), bottom.data_ptr(),
                                                                             dx_ptr=self.dx.data_ptr() if self.dx is not None else 0,
                                                                             dc_ptr=self.dc.data_ptr() if self.dc is not None else 0, floor=float(floor), stream=s))
+        _warmed(nlp, cold)
         return top, bottom
 
     def block_preconditioner(self, floor=1e-10):
         """KKTBlockPreconditioner: M^-1 = blockdiag_k(P_k^T L_k^-T |D_k|^-1 L_k^-1 P_k) (+) diag(top of the six globals) (+) diag(bottom),
-        ready for solve(minv=...).  TWO launches: the per-knot Bunch-Kaufman factorisation of H_k + diag dx_k (hipnlp_kkt_block_factor_device,
+        ready for solve(minv=...).  Graph capture: replayable after one eager call on the handle.
+        TWO launches: the per-knot Bunch-Kaufman factorisation of H_k + diag dx_k (hipnlp_kkt_block_factor_device,
         one workgroup per knot and trajectory) and the diagonal launch of diagonal_preconditioner (its bottom and its six globals' top
         elements, bit for bit).  .inertia [batch, N, 3] int32 (positive, negative, zero eigenvalues of every H_k + dx_k) and .status
         [batch, N] int32 (0 factored, 2 data not finite: that knot's 189 elements come out of apply as NaN, solve: status 2); nothing is
@@ -312,6 +400,7 @@ class KKTValues:
         torch, nlp = _torch(), self.nlp
         if not (isinstance(floor, numbers.Real) and not isinstance(floor, bool) and 0.0 < floor < float("inf")):
             raise ValueError("floor: a finite real number > 0, not %r" % (floor,))
+        cold = _enter(nlp, "KKTValues.block_preconditioner", "kkt_block_factor", "kkt_diag_precond")
         dev, nbytes = self.hess.device, nlp.engine.kkt_block_bytes()
         N = (nlp.n - 6) // self.ORDER                                          # knots: n = 189 N + the six globals
         factor = torch.empty((nlp.batch, N, nbytes[0] // (8 * nlp.batch * N)), dtype=torch.float64, device=dev)
@@ -325,6 +414,7 @@ class KKTValues:
                                                                             inertia.data_ptr(), status.data_ptr(), dx_ptr=self.dx.data_ptr() if self.dx is not None else 0,
                                                                             floor=float(floor), stream=s))
         top, bottom = self.diagonal_preconditioner(floor)
+        _warmed(nlp, cold)
         return KKTBlockPreconditioner(self, factor, pivots, e, o, inertia, status, top, bottom)
 
     def convexify(self, delta_init=1e-4, kappa=8.0, max_tries=16, floor=1e-10):
@@ -349,7 +439,8 @@ class KKTValues:
         its whole block positive definite, which can take more; nor that MINRES converges on .values, with this preconditioner or any
         other.  delta_init and kappa default to IPOPT's first_hessian_perturbation and perturb_inc_fact; nobody has tuned them here, nor
         floor.  Cost: (tries + 1) factorisations for the slowest knot of the launch; measured: profiles/r17_kkt_ladder.txt.
-        max_tries = 0 is block_preconditioner with delta 0 and tries 0.  Nothing is synchronised: all attributes are device tensors."""
+        max_tries = 0 is block_preconditioner with delta 0 and tries 0.  Nothing is synchronised: all attributes are device tensors.
+        Graph capture: replayable whole, its torch operations included, after one eager call on the handle."""
         torch, nlp = _torch(), self.nlp
         floor = _checked_floor(floor)
         if not (isinstance(max_tries, numbers.Integral) and not isinstance(max_tries, bool) and 0 <= max_tries <= 16):
@@ -358,6 +449,7 @@ class KKTValues:
             raise ValueError("delta_init: a finite real number > 0, not %r" % (delta_init,))
         if not (isinstance(kappa, numbers.Real) and not isinstance(kappa, bool) and 1.0 < kappa < float("inf")):
             raise ValueError("kappa: a finite real number > 1, not %r" % (kappa,))
+        cold = _enter(nlp, "KKTValues.convexify", "kkt_block_ladder", "kkt_diag_precond")
         dev, nbytes = self.hess.device, nlp.engine.kkt_block_bytes()
         N = (nlp.n - 6) // self.ORDER                                          # knots: n = 189 N + the six globals
         factor = torch.empty((nlp.batch, N, nbytes[0] // (8 * nlp.batch * N)), dtype=torch.float64, device=dev)
@@ -374,12 +466,14 @@ class KKTValues:
                                                                             dx_ptr=self.dx.data_ptr() if self.dx is not None else 0, floor=floor,
                                                                             delta_init=float(delta_init), kappa=float(kappa), max_tries=int(max_tries), stream=s))
         dx = torch.zeros((nlp.batch, nlp.n), dtype=torch.float64, device=dev) if self.dx is None else self.dx.clone()
-        dx[:, :self.ORDER * N] += delta.repeat_interleave(self.ORDER, dim=1)
+        dx[:, :self.ORDER * N] += delta[:, :, None].expand(-1, -1, self.ORDER).reshape(nlp.batch, self.ORDER * N)   # (delta_k on knot k's 189 variables)
         convex = self.with_diagonals(dx, self.dc)
         top, bottom = convex.diagonal_preconditioner(floor)
-        wanted = torch.tensor([self.ORDER, 0, 0], dtype=torch.int32, device=dev)
-        quasi = (status == 0).all(dim=1) & (inertia == wanted).all(dim=2).all(dim=1) & (dx[:, self.ORDER * N:] > 0.0).all(dim=1)
+        # (compared with numbers, not with a tensor built from a list: that is a copy from host memory, which a capture forbids)
+        positive = (inertia[:, :, 0] == self.ORDER) & (inertia[:, :, 1] == 0) & (inertia[:, :, 2] == 0)
+        quasi = (status == 0).all(dim=1) & positive.all(dim=1) & (dx[:, self.ORDER * N:] > 0.0).all(dim=1)
         quasi = quasi & (self.dc > 0.0).all(dim=1) if self.dc is not None else torch.zeros_like(quasi)
+        _warmed(nlp, cold)
         return KKTBlockPreconditioner(convex, factor, pivots, e, o, inertia, status, top, bottom, delta=delta, tries=tries, quasi_definite=quasi)
 
     def condensed_preconditioner(self, floor=1e-10):
@@ -401,11 +495,13 @@ class KKTValues:
         same; at 100 x 1 and 100 x 64 (planar) every trajectory converges within 3 000 iterations at both scales (556; 282 - 1 017) where
         the block preconditioner does not; on the stairs at 200 x 16 nothing converges.  NOT claimed: convergence at other shapes or diagonals; that an interior-point
         step is cheap with it; any inertia correction (a ladder on B_k is not built); anything about the off-diagonal blocks of C — a
-        block-tridiagonal factorisation would be the exact inverse of C, this is not.  Nothing is synchronised."""
+        block-tridiagonal factorisation would be the exact inverse of C, this is not.  Nothing is synchronised.  Graph capture: replayable
+        after one eager call on the handle."""
         torch, nlp = _torch(), self.nlp
         floor = _checked_floor(floor)
         if self.dc is None:
             raise ValueError("condensed_preconditioner: the condensed block eliminates the bottom block, which needs dc > 0 — these values have no dc (with_diagonals)")
+        cold = _enter(nlp, "KKTValues.condensed_preconditioner", "kkt_condensed_factor")
         dev, nbytes = self.hess.device, nlp.engine.kkt_block_bytes()
         N = (nlp.n - 6) // self.ORDER                                          # knots: n = 189 N + the six globals
         factor = torch.empty((nlp.batch, N, nbytes[0] // (8 * nlp.batch * N)), dtype=torch.float64, device=dev)
@@ -420,6 +516,7 @@ class KKTValues:
         nlp._on_current_stream(lambda s: nlp.engine.kkt_condensed_factor_device(self.hess.data_ptr(), self.jac.data_ptr(), self.dc.data_ptr(), factor.data_ptr(), pivots.data_ptr(),
                                                                                 e.data_ptr(), o.data_ptr(), inertia.data_ptr(), status.data_ptr(), top.data_ptr(), bottom.data_ptr(),
                                                                                 dx_ptr=self.dx.data_ptr() if self.dx is not None else 0, floor=floor, stream=s))
+        _warmed(nlp, cold)
         pre = KKTBlockPreconditioner(self, factor, pivots, e, o, inertia, status, top, bottom)
         pre.condensed = True
         return pre
@@ -440,7 +537,11 @@ class KKTValues:
         rescaled synthetic systems K' = S K S with cond 1e12 converge in the 23 to 25 iterations of the unscaled system where the
         identity stands at a residual of 4e-2 after 300; on the real N = 4 value runs of the stairs terrain (cond 3e9) status 0 after
         2194 iterations where the identity has residual 0.47 after 3000, on the planar terrain about a fifth fewer iterations than the
-        identity's 2123.  That does not make an interior-point step cheap; larger systems: profiles/r13_kkt_precond.txt."""
+        identity's 2123.  That does not make an interior-point step cheap; larger systems: profiles/r13_kkt_precond.txt.
+        Graph capture: with check_every=0 replayable after one eager call on the handle with the same kind of minv — every replay starts
+        from zero (iteration 0 resets the workspace's records), whatever status the previous one or an eager solve in between left;
+        the solves and replays of one nlp share the workspace, so keep them on one stream or ordered.  check_every > 0 waits for the
+        stream in the middle of the launches and is refused while capturing (RuntimeError)."""
         torch, nlp = _torch(), self.nlp
         nlp._check("rhs_top", rhs_top, (nlp.batch, nlp.n))
         nlp._check("rhs_bottom", rhs_bottom, (nlp.batch, nlp.m))
@@ -460,6 +561,11 @@ class KKTValues:
             mt, mb = minv
             nlp._check("minv top", mt, (nlp.batch, nlp.n))
             nlp._check("minv bottom", mb, (nlp.batch, nlp.m))
+        if check_every > 0:
+            _refuse("KKTValues.solve(check_every=%d)" % check_every, "it waits for the stream (hipStreamSynchronize) after every check_every iterations, in the middle "
+                        "of the launches, which would invalidate the capture with part of the chain recorded", "Pass check_every=0: all maxiter iterations are enqueued "
+                        "without a wait, a trajectory that has a status is frozen, and the bits are the same")
+        cold = _enter(nlp, "KKTValues.solve", "kkt_minres_block" if blk is not None else ("kkt_minres", "minv" if mt is not None else "no minv"))
         top = torch.empty_like(rhs_top, memory_format=torch.contiguous_format)
         bottom = torch.empty_like(rhs_bottom, memory_format=torch.contiguous_format)
         iterations = torch.empty((nlp.batch,), dtype=torch.int32, device=nlp.device)
@@ -471,12 +577,14 @@ class KKTValues:
                 rhs_top.data_ptr(), rhs_bottom.data_ptr(), top.data_ptr(), bottom.data_ptr(), iterations.data_ptr(), residual.data_ptr(), status.data_ptr(),
                 dx_ptr=self.dx.data_ptr() if self.dx is not None else 0, dc_ptr=self.dc.data_ptr() if self.dc is not None else 0, rtol=rtol, max_iterations=maxiter,
                 check_every=check_every, stream=s))
+            _warmed(nlp, cold)
             return KKTSolution(top, bottom, iterations, residual, status)
         nlp._on_current_stream(lambda s: nlp.engine.kkt_minres_device(
             self.hess.data_ptr(), self.jac.data_ptr(), rhs_top.data_ptr(), rhs_bottom.data_ptr(), top.data_ptr(), bottom.data_ptr(), iterations.data_ptr(),
             residual.data_ptr(), status.data_ptr(), dx_ptr=self.dx.data_ptr() if self.dx is not None else 0, dc_ptr=self.dc.data_ptr() if self.dc is not None else 0,
             minv_top_ptr=mt.data_ptr() if mt is not None else 0, minv_bottom_ptr=mb.data_ptr() if mb is not None else 0, rtol=rtol, max_iterations=maxiter,
             check_every=check_every, stream=s))
+        _warmed(nlp, cold)
         return KKTSolution(top, bottom, iterations, residual, status)
 
 
@@ -503,15 +611,18 @@ class KKTBlockPreconditioner:
         self.delta, self.tries, self.quasi_definite = delta, tries, quasi_definite
 
     def apply(self, r_top, r_bottom):
-        """(z_top [batch, n], z_bottom [batch, m]) = M^-1 [r_top; r_bottom], one launch; a knot with status 2 yields NaN for its 189 elements"""
+        """(z_top [batch, n], z_bottom [batch, m]) = M^-1 [r_top; r_bottom], one launch; a knot with status 2 yields NaN for its 189 elements.
+        Graph capture: replayable after one eager call on the handle."""
         torch, nlp = _torch(), self.nlp
         nlp._check("r_top", r_top, (nlp.batch, nlp.n))
         nlp._check("r_bottom", r_bottom, (nlp.batch, nlp.m))
+        cold = _enter(nlp, "KKTBlockPreconditioner.apply", "kkt_block_apply")
         z_top = torch.empty_like(r_top, memory_format=torch.contiguous_format)
         z_bottom = torch.empty_like(r_bottom, memory_format=torch.contiguous_format)
         nlp._on_current_stream(lambda s: nlp.engine.kkt_block_apply_device(self.factor.data_ptr(), self.pivots.data_ptr(), self.e.data_ptr(), self.o.data_ptr(),
                                                                            self.top_diagonal.data_ptr(), self.bottom.data_ptr(), r_top.data_ptr(), r_bottom.data_ptr(),
                                                                            z_top.data_ptr(), z_bottom.data_ptr(), stream=s))
+        _warmed(nlp, cold)
         return z_top, z_bottom
 
 
@@ -546,14 +657,17 @@ class PoseKKTValues:
         return PoseKKTValues(self.nlp, self.hess, self.jac, dx, dc)
 
     def matvec(self, v, w):
-        """(top [batch, 81], bottom [batch, m]) = K [v; w], v [batch, 81], w [batch, m]; one launch (hipnlp_pose_kkt_times_device)"""
+        """(top [batch, 81], bottom [batch, m]) = K [v; w], v [batch, 81], w [batch, m]; one launch (hipnlp_pose_kkt_times_device).
+        Graph capture: replayable after one eager call on the handle."""
         torch, nlp = _torch(), self.nlp
         nlp._check("v", v, (nlp.batch, nlp.n))
         nlp._check("w", w, (nlp.batch, nlp.m))
+        cold = _enter(nlp, "PoseKKTValues.matvec", "kkt_times")
         top = torch.empty_like(v, memory_format=torch.contiguous_format)
         bottom = torch.empty_like(w, memory_format=torch.contiguous_format)
         nlp._on_current_stream(lambda s: nlp.engine.kkt_times_device(self.hess.data_ptr(), self.jac.data_ptr(), v.data_ptr(), w.data_ptr(), top.data_ptr(), bottom.data_ptr(),
                                                                      stream=s, **self._diagonals()))
+        _warmed(nlp, cold)
         return top, bottom
 
     def diagonal_preconditioner(self, floor=1e-10):
@@ -561,13 +675,15 @@ class PoseKKTValues:
         pattern has no diagonal entry) and bottom = 1 / max(|dc + sum_e J_ie^2 top_col(e)|, floor), one launch
         (hipnlp_pose_kkt_diag_precond_device).  floor > 0 keeps the reciprocals finite; its default is a guess nobody has tuned.  A NaN or
         an infinity in the value runs or diagonals comes out as NaN (solve: status 2).  solve(minv="diagonal") builds the same diagonal
-        inside the solve's own launch."""
+        inside the solve's own launch.  Graph capture: replayable after one eager call on the handle."""
         torch, nlp = _torch(), self.nlp
         floor = _checked_floor(floor)
+        cold = _enter(nlp, "PoseKKTValues.diagonal_preconditioner", "kkt_diag_precond")
         top = torch.empty((nlp.batch, nlp.n), dtype=torch.float64, device=self.hess.device)
         bottom = torch.empty((nlp.batch, nlp.m), dtype=torch.float64, device=self.hess.device)
         nlp._on_current_stream(lambda s: nlp.engine.kkt_diag_precond_device(self.hess.data_ptr(), self.jac.data_ptr(), top.data_ptr(), bottom.data_ptr(), floor=floor,
                                                                             stream=s, **self._diagonals()))
+        _warmed(nlp, cold)
         return top, bottom
 
     def solve(self, rhs_top, rhs_bottom, rtol=1e-8, maxiter=400, minv=None, floor=1e-10):
@@ -579,7 +695,8 @@ class PoseKKTValues:
         1: maxiter (at most 4096) reached; 2: breakdown (minv not positive, or data that is not finite).  Not recorded by autograd.
         Measured with the CPU emulation of this launch (rtol 1e-8, dx and dc in U[1, 2] — not an interior-point method's): the real
         value runs of three poses of each of six settings variants, cond(K) 1e3 to 5e6, converge with minv="diagonal" in 75 to 349
-        iterations, all eighteen; timings: profiles/r14_pose_kkt.txt."""
+        iterations, all eighteen; timings: profiles/r14_pose_kkt.txt.  Graph capture: replayable after one eager call on the handle (one
+        launch, no workspace, nothing carried from one solve to the next)."""
         torch, nlp = _torch(), self.nlp
         nlp._check("rhs_top", rhs_top, (nlp.batch, nlp.n))
         nlp._check("rhs_bottom", rhs_bottom, (nlp.batch, nlp.m))
@@ -599,6 +716,7 @@ class PoseKKTValues:
             mt, mb = minv
             nlp._check("minv top", mt, (nlp.batch, nlp.n))
             nlp._check("minv bottom", mb, (nlp.batch, nlp.m))
+        cold = _enter(nlp, "PoseKKTValues.solve", ("kkt_minres", "diagonal built" if build else "minv" if mt is not None else "no minv"))
         top = torch.empty_like(rhs_top, memory_format=torch.contiguous_format)
         bottom = torch.empty_like(rhs_bottom, memory_format=torch.contiguous_format)
         iterations = torch.empty((nlp.batch,), dtype=torch.int32, device=nlp.device)
@@ -608,6 +726,7 @@ class PoseKKTValues:
             self.hess.data_ptr(), self.jac.data_ptr(), rhs_top.data_ptr(), rhs_bottom.data_ptr(), top.data_ptr(), bottom.data_ptr(), iterations.data_ptr(),
             residual.data_ptr(), status.data_ptr(), minv_top_ptr=mt.data_ptr() if mt is not None else 0, minv_bottom_ptr=mb.data_ptr() if mb is not None else 0,
             build_diagonal=build, floor=floor, rtol=float(rtol), max_iterations=int(maxiter), stream=s, **self._diagonals()))
+        _warmed(nlp, cold)
         return KKTSolution(top, bottom, iterations, residual, status)
 
 
@@ -643,6 +762,8 @@ class PoseKKTValues:
         top = bottom = None
         if rhs_top is not None:
             nrhs, _ = self._rhs(rhs_top, rhs_bottom)
+        cold = _enter(nlp, "PoseKKTValues.%s" % ("factor" if store else "solve_direct"), ("kkt_ldl", "factor stored" if store else "solve"))
+        if rhs_top is not None:
             top = torch.empty_like(rhs_top, memory_format=torch.contiguous_format)
             bottom = torch.empty_like(rhs_bottom, memory_format=torch.contiguous_format)
         dev = self.hess.device
@@ -659,6 +780,7 @@ class PoseKKTValues:
             self.hess.data_ptr(), self.jac.data_ptr(), inertia.data_ptr(), status.data_ptr(), nrhs=nrhs, rhs_top_ptr=ptr(rhs_top), rhs_bottom_ptr=ptr(rhs_bottom),
             sol_top_ptr=ptr(top), sol_bottom_ptr=ptr(bottom), delta_ptr=delta.data_ptr(), tries_ptr=tries.data_ptr(), delta_init=delta_init, kappa=kappa, max_tries=max_tries,
             factor_ptr=ptr(factor), pivots_ptr=ptr(pivots), stream=s, **self._diagonals()))
+        _warmed(nlp, cold)
         return top, bottom, inertia, status, delta, tries, factor, pivots
 
     def factor(self, delta_init=None, kappa=8.0, max_tries=0):
@@ -666,7 +788,8 @@ class PoseKKTValues:
         (hipnlp_pose_kkt_ldl_device), with .inertia [batch, 3] int32 (positive, negative, zero eigenvalues), .status [batch] int32
         (0 factored, 1 exactly singular, 2 data not finite, 3 ladder exhausted), .delta [batch] and .tries [batch] int32.
         max_tries = 0: factor once, report the inertia as it is.  max_tries > 0 (at most 16): IPOPT's inertia correction on the top
-        block — try t >= 1 adds delta_init kappa^(t-1) to its diagonal — until the inertia is (81, m, 0).  Timings: profiles/r15_pose_ldl.txt."""
+        block — try t >= 1 adds delta_init kappa^(t-1) to its diagonal — until the inertia is (81, m, 0).  Timings: profiles/r15_pose_ldl.txt.
+        Graph capture: replayable after one eager call on the handle."""
         ladder = self._ladder(delta_init, kappa, max_tries)
         _, _, inertia, status, delta, tries, factor, pivots = self._ldl(None, None, ladder, True)
         return PoseKKTFactor(self, factor, pivots, inertia, status, delta, tries, regularised=ladder[2] > 0)
@@ -674,7 +797,8 @@ class PoseKKTValues:
     def solve_direct(self, rhs_top, rhs_bottom, delta_init=None, kappa=8.0, max_tries=0):
         """(top, bottom, inertia [batch, 3] int32, status [batch] int32): factor (with the ladder of `factor`) and solve in ONE launch,
         no factor stored; right-hand sides [batch, 81] / [batch, m] or [batch, nrhs, 81] / [batch, nrhs, m], nrhs <= 8.  With status 1
-        or 2 the solution is NaN; with a delta > 0 it is the solution of the regularised system."""
+        or 2 the solution is NaN; with a delta > 0 it is the solution of the regularised system.  Graph capture: replayable after one
+        eager call on the handle."""
         ladder = self._ladder(delta_init, kappa, max_tries)
         top, bottom, inertia, status, _, _, _, _ = self._ldl(rhs_top, rhs_bottom, ladder, False)
         return top, bottom, inertia, status
@@ -691,10 +815,12 @@ class PoseKKTFactor:
 
     def _solve(self, rhs_top, rhs_bottom, nrhs):
         torch, nlp = _torch(), self.values.nlp
+        cold = _enter(nlp, "PoseKKTFactor.solve", "kkt_ldl_solve")
         top = torch.empty_like(rhs_top, memory_format=torch.contiguous_format)
         bottom = torch.empty_like(rhs_bottom, memory_format=torch.contiguous_format)
         nlp._on_current_stream(lambda s: nlp.engine.kkt_ldl_solve_device(self.factor.data_ptr(), self.pivots.data_ptr(), nrhs, rhs_top.data_ptr(), rhs_bottom.data_ptr(),
                                                                          top.data_ptr(), bottom.data_ptr(), stream=s))
+        _warmed(nlp, cold)
         return top, bottom
 
     def solve(self, rhs_top, rhs_bottom, refine=0):
@@ -703,11 +829,13 @@ class PoseKKTFactor:
         existing launches: r = b - K z by the one-launch matvec (hipnlp_pose_kkt_times_device), a solve of r from the factor, z += it.
         The ladder's delta is in the FACTOR only: the values' operator has their own dx.  So where a ladder was asked for, the
         refinement runs against dx + delta — it converges to the solution of the REGULARISED system; it converges to the solution of
-        the unregularised system only where delta = 0."""
+        the unregularised system only where delta = 0.  Graph capture: replayable, the refinement's torch operations included, after one
+        eager call on the handle (with refine > 0 where the capture has it: the refinement launches the matvec too)."""
         torch, v = _torch(), self.values
         nrhs, flat = v._rhs(rhs_top, rhs_bottom)
         if not (isinstance(refine, numbers.Integral) and not isinstance(refine, bool) and refine >= 0):
             raise ValueError("refine: an integer >= 0, not %r" % (refine,))
+        _enter(v.nlp, "PoseKKTFactor.solve", "kkt_ldl_solve", *(("kkt_times",) if refine else ()))   # (both, before the first launch)
         top, bottom = self._solve(rhs_top, rhs_bottom, nrhs)
         if refine:
             op = v
@@ -740,7 +868,9 @@ class _DeviceNLP:
         return _torch().device("cuda", self.device_index)
 
     def set_params(self, p):
-        """p [batch, np] (numpy array or tensor): the parameters of every trajectory"""
+        """p [batch, np] (numpy array or tensor): the parameters of every trajectory.  Graph capture: not replayable (a synchronous host
+        copy), refused while capturing."""
+        _refuse("set_params", "it copies from host memory and waits for the stream", "Set the parameters outside the capture")
         if hasattr(p, "detach"):
             p = p.detach().cpu().numpy()
         self.engine.set_params(np.asarray(p, dtype=np.float64))
@@ -754,12 +884,16 @@ class _DeviceNLP:
     def _on_current_stream(self, launch):
         """launch(stream handle), ordered on torch.cuda.current_stream().  A NULL stream means the handle's OWN stream to the library
         (include/hipnlp.h), so on torch's default stream the launch goes to a private stream that waits for the current one, and the
-        current one waits for it (tensors are allocated on the current stream: nothing of it runs before the launch has ended)."""
+        current one waits for it (tensors are allocated on the current stream: nothing of it runs before the launch has ended).  That
+        fork and join must never be captured (parallel branches in a graph); a capture has a stream of its own, so it never is."""
         torch = _torch()
         cur = torch.cuda.current_stream(self.device)
         if cur.cuda_stream:
             launch(cur.cuda_stream)
             return
+        if _capturing():
+            raise RuntimeError("a capture on the default stream: the launch would fork to the handle's side stream and join, a graph with parallel branches.  "
+                               "Capture on a stream of its own (torch.cuda.graph does)")
         if getattr(self, "_side", None) is None:
             self._side = torch.cuda.Stream(device=self.device)
         self._side.wait_stream(cur)
@@ -794,14 +928,30 @@ class KinodynamicNLP(_DeviceNLP):
         self.jacobian_products = bool(jacobian_products)
 
     def __call__(self, x):
-        """(f [batch], g [batch, m]); differentiable in x"""
+        """(f [batch], g [batch, m]); differentiable in x.  Graph capture: NOT replayable, refused while capturing (RuntimeError) — the
+        launch sums f in a reducer workgroup that accepts a knot's partial by the launch number (hipnlp.hip: pub_pattern(a.seq)); a
+        captured launch bakes that number in, every partial of the previous replay still carries it, and the reducer may sum the
+        previous x's partials: a stale or mixed f with no error.  Its backward and double backward passes are refused too (they are
+        the launches of lagrangian_gradient and hessian_vector_product, and no test replays what autograd's engine enqueues) — where
+        the guard can see the capture: a backward node runs on its forward pass's stream, so that is where the forward pass ran on the
+        capturing stream; with the forward pass on another stream the guard is silent and the capture error is torch's own."""
         self._check("x", x, (self.batch, self.n))
         return _function().apply(x, self)
 
+    def _enter_forward(self):
+        _refuse("KinodynamicNLP.__call__", _EVAL_SEQ, "Evaluate nlp(x) outside the capture; everything on stored value runs (jacobian(x) / hessian(...) / kkt(...) "
+                     "taken outside the capture) can be captured")
+
     def lagrangian_gradient(self, x, sigma, lam):
-        """sigma grad f(x) + J(x)^T lam per trajectory ([batch, n]): sigma a number or a [batch] tensor, lam [batch, m]"""
+        """sigma grad f(x) + J(x)^T lam per trajectory ([batch, n]): sigma a number or a [batch] tensor, lam [batch, m].
+        Graph capture: NOT replayable, refused while capturing (RuntimeError) — for lack of a reference, not because anything was seen
+        to go wrong: the launch evaluates the model at x, and no
+        CPU reference gives the bits of such a kernel (tests/*_emu_lib.py are bitwise only for the launches on stored value runs), so the
+        replay test cannot be run for it.  (Read from the code: everything reaches the kernel through pointers; the launch number
+        only feeds the non-finite generation flag atomicMax(a.flag + b, a.seq), which nothing in this module reads.)"""
         torch = _torch()
         self._check("x", x, (self.batch, self.n))
+        _refuse("KinodynamicNLP.lagrangian_gradient", _NO_REFERENCE, _STORED)
         if isinstance(sigma, numbers.Real):
             sigma = torch.full((self.batch,), float(sigma), dtype=torch.float64, device=self.device)
         self._check("sigma", sigma, (self.batch,))
@@ -814,9 +964,14 @@ class KinodynamicNLP(_DeviceNLP):
 
     def jacobian(self, x):
         """JacobianValues at x: one hipnlp_eval_device launch with grad f and jac g into tensors; .matvec / .grad_dot / .jvp / .rmatvec
-        multiply them, one launch each.  Not recorded by autograd."""
+        multiply them, one launch each.  Not recorded by autograd.  Graph capture: NOT replayable, refused while capturing (RuntimeError):
+        the launch is hipnlp_eval_device, which always runs the cost reducer on a captured launch number (__call__), stores only the
+        VARYING entries of jac g into a destination that the handle's own table remembers as filled with the constant ones (hipnlp.hip,
+        hipnlp_eval_device: dfilled) and takes those constants from a template that set_params frees and allocates again.  Take
+        jacobian(x) outside the capture; the products of the returned JacobianValues are replayable."""
         torch = _torch()
         self._check("x", x, (self.batch, self.n))
+        _refuse("KinodynamicNLP.jacobian", _EVAL_JAC, "Take jacobian(x) outside the capture and capture the products on its value run")
         grad = torch.empty(self.batch, self.n, dtype=torch.float64, device=self.device)
         values = torch.empty(self.batch, self.engine.nnz, dtype=torch.float64, device=self.device)
         self._on_current_stream(lambda s: self.engine.eval_device(x.data_ptr(), 0, grad.data_ptr(), 0, values.data_ptr(), stream=s))
@@ -825,34 +980,53 @@ class KinodynamicNLP(_DeviceNLP):
     def jacobian_vector_product(self, x, v):
         """(grad f(x) . v [batch], J(x) v [batch, m]) per trajectory, v [batch, n].  TWO launches — hipnlp_eval_device writes grad f and
         jac g, hipnlp_jac_times_device multiplies them (there is no fused one-launch product for this NLP); for many products at one x
-        keep jacobian(x).  Not recorded by autograd."""
+        keep jacobian(x).  Not recorded by autograd.  Graph capture: NOT replayable, refused while capturing (RuntimeError): its first
+        launch is jacobian(x)'s."""
         self._check("x", x, (self.batch, self.n))
         self._check("v", v, (self.batch, self.n))
+        _refuse("KinodynamicNLP.jacobian_vector_product", _EVAL_JAC, "Take J = jacobian(x) outside the capture and capture J.jvp(v)")
         return self.jacobian(x).jvp(v)
 
     def hessian_vector_product(self, x, sigma, lam, v):
         """H(x, sigma, lam) v per trajectory ([batch, n]), H the Hessian of sigma f + lam . g in x: sigma a number or a [batch] tensor,
-        lam [batch, m], v [batch, n].  One launch; H is never written.  Not recorded by autograd."""
+        lam [batch, m], v [batch, n].  One launch; H is never written.  Not recorded by autograd.
+        Graph capture: NOT replayable, refused while capturing (RuntimeError) — for lack of a reference, not because anything was seen
+        to go wrong: the launch evaluates the model at x, and no
+        CPU reference gives the bits of such a kernel (tests/*_emu_lib.py are bitwise only for the launches on stored value runs), so the
+        replay test cannot be run for it.  (Read from the code: the launch number only feeds the non-finite generation flag, which
+        nothing in this module reads.)"""
         self._check("x", x, (self.batch, self.n))
+        _refuse("KinodynamicNLP.hessian_vector_product", _NO_REFERENCE, _STORED)
         sigma = self._sigma(sigma)
         self._check("lam", lam, (self.batch, self.m))
         self._check("v", v, (self.batch, self.n))
         return self._launch_hvp(x, sigma, lam, v)
 
     def hessian(self, x, sigma, lam):
-        """HessianValues at (x, sigma, lam): one hipnlp_eval_hess_device launch; .matvec(v) is bit for bit hessian_vector_product(..., v)"""
+        """HessianValues at (x, sigma, lam): one hipnlp_eval_hess_device launch; .matvec(v) is bit for bit hessian_vector_product(..., v).
+        Graph capture: NOT replayable, refused while capturing (RuntimeError) — for lack of a reference, not because anything was seen
+        to go wrong: the launch evaluates the model at x, and no
+        CPU reference gives the bits of such a kernel (tests/*_emu_lib.py are bitwise only for the launches on stored value runs), so the
+        replay test cannot be run for it.  (Read from the code: the launch number only feeds the non-finite generation flag, which
+        nothing in this module reads.)  Take hessian(...) outside the capture; .matvec on it is replayable."""
         torch = _torch()
         self._check("x", x, (self.batch, self.n))
+        _refuse("KinodynamicNLP.hessian", _NO_REFERENCE, _STORED)
+        cold = _enter(self, "KinodynamicNLP.hessian", "hess_nnz")
         sigma = self._sigma(sigma)
         self._check("lam", lam, (self.batch, self.m))
         values = torch.empty(self.batch, self.engine.hess_nnz(), dtype=torch.float64, device=self.device)
         self._on_current_stream(lambda s: self.engine.eval_hess_device(x.data_ptr(), sigma.data_ptr(), lam.data_ptr(), values.data_ptr(), stream=s))
+        _warmed(self, cold)
         return HessianValues(self, values)
 
     def kkt(self, x, sigma, lam, dx=None, dc=None):
         """KKTValues at (x, sigma, lam) with the diagonals dx [batch, n] and dc [batch, m] (None: left out): the two evaluation launches
         of jacobian(x) and hessian(x, sigma, lam); .matvec(v, w) applies [[H + diag dx, J^T], [J, -diag dc]] in one launch.  Not recorded
-        by autograd."""
+        by autograd.  Graph capture: NOT replayable, refused while capturing (RuntimeError): one of its launches is jacobian(x)'s.  Take
+        kkt(...) outside the capture; everything on the returned KKTValues is replayable (solve: with check_every=0), as is
+        KKTValues(nlp, H, J, dx, dc) on value runs taken outside."""
+        _refuse("KinodynamicNLP.kkt", _EVAL_JAC, "Take kkt(...) outside the capture and capture what runs on it: matvec, the preconditioners, solve(check_every=0)")
         return KKTValues(self, self.hessian(x, sigma, lam), self.jacobian(x), dx, dc)
 
     # ---- internals ------------------------------------------------------------------------------------------------------------------
@@ -882,15 +1056,29 @@ class PoseNLP(_DeviceNLP):
         self.device_index = int(device)
 
     def __call__(self, x):
-        """(f [batch], g [batch, m]); differentiable in x"""
+        """(f [batch], g [batch, m]); differentiable in x.
+        Graph capture: NOT replayable, refused while capturing (RuntimeError) — for lack of a reference, not because anything was seen
+        to go wrong: the launch evaluates the model at x, and no
+        CPU reference gives the bits of such a kernel (tests/*_emu_lib.py are bitwise only for the launches on stored value runs), so the
+        replay test cannot be run for it.  (Read from the code: a pose's workgroup sums its own f and no launch number is involved;
+        nothing is allocated after hipnlp_pose_create.)  The backward and double backward passes are refused too, where their forward
+        pass ran on the capturing stream (KinodynamicNLP.__call__)."""
         self._check("x", x, (self.batch, self.n))
         return _function().apply(x, self)
 
+    def _enter_forward(self):
+        _refuse("PoseNLP.__call__", _NO_REFERENCE, _STORED)
+
     def lagrangian_gradient(self, x, sigma, lam):
         """sigma grad f(x) + J(x)^T lam per pose ([batch, 81]): sigma a number or a [batch] tensor, lam [batch, m].  Differentiable in x,
-        sigma and lam where they require grad."""
+        sigma and lam where they require grad.
+        Graph capture: NOT replayable, refused while capturing (RuntimeError) — for lack of a reference, not because anything was seen
+        to go wrong: the launch evaluates the model at x, and no
+        CPU reference gives the bits of such a kernel (tests/*_emu_lib.py are bitwise only for the launches on stored value runs), so the
+        replay test cannot be run for it."""
         torch = _torch()
         self._check("x", x, (self.batch, self.n))
+        _refuse("PoseNLP.lagrangian_gradient", _NO_REFERENCE, _STORED)
         sigma = self._sigma(sigma)
         self._check("lam", lam, (self.batch, self.m))
         if (x.requires_grad or sigma.requires_grad or lam.requires_grad) and torch.is_grad_enabled():
@@ -898,15 +1086,25 @@ class PoseNLP(_DeviceNLP):
         return self._launch(x, sigma, lam)
 
     def jacobian_vector_product(self, x, v):
-        """(grad f(x) . v [batch], J(x) v [batch, m]) per pose, v [batch, 81].  One launch; jac g is never written.  Not recorded by autograd."""
+        """(grad f(x) . v [batch], J(x) v [batch, m]) per pose, v [batch, 81].  One launch; jac g is never written.  Not recorded by autograd.
+        Graph capture: NOT replayable, refused while capturing (RuntimeError) — for lack of a reference, not because anything was seen
+        to go wrong: the launch evaluates the model at x, and no
+        CPU reference gives the bits of such a kernel (tests/*_emu_lib.py are bitwise only for the launches on stored value runs), so the
+        replay test cannot be run for it."""
         self._check("x", x, (self.batch, self.n))
         self._check("v", v, (self.batch, self.n))
+        _refuse("PoseNLP.jacobian_vector_product", _NO_REFERENCE, _STORED)
         return self._launch_jvp(x, v, True, True)
 
     def hessian_vector_product(self, x, sigma, lam, v):
         """H(x, sigma, lam) v per pose ([batch, 81]), H the Hessian of sigma f + lam . g in x: sigma a number or a [batch] tensor,
-        lam [batch, m], v [batch, 81].  One launch; H is never written.  Not recorded by autograd."""
+        lam [batch, m], v [batch, 81].  One launch; H is never written.  Not recorded by autograd.
+        Graph capture: NOT replayable, refused while capturing (RuntimeError) — for lack of a reference, not because anything was seen
+        to go wrong: the launch evaluates the model at x, and no
+        CPU reference gives the bits of such a kernel (tests/*_emu_lib.py are bitwise only for the launches on stored value runs), so the
+        replay test cannot be run for it."""
         self._check("x", x, (self.batch, self.n))
+        _refuse("PoseNLP.hessian_vector_product", _NO_REFERENCE, _STORED)
         sigma = self._sigma(sigma)
         self._check("lam", lam, (self.batch, self.m))
         self._check("v", v, (self.batch, self.n))
@@ -922,9 +1120,14 @@ class PoseNLP(_DeviceNLP):
     def kkt(self, x, sigma, lam, dx=None, dc=None):
         """PoseKKTValues at (x, sigma, lam) with the diagonals dx [batch, 81] and dc [batch, m] (None: left out): two evaluation launches
         (hipnlp_pose_eval_device for jac g, hipnlp_pose_eval_hess_device) whose value runs it keeps; .matvec(v, w),
-        .diagonal_preconditioner() and .solve(rhs_top, rhs_bottom) are one launch each.  Not recorded by autograd."""
+        .diagonal_preconditioner() and .solve(rhs_top, rhs_bottom) are one launch each.  Not recorded by autograd.
+        Graph capture: NOT replayable, refused while capturing (RuntimeError) — for lack of a reference, not because anything was seen
+        to go wrong: the launch evaluates the model at x, and no
+        CPU reference gives the bits of such a kernel (tests/*_emu_lib.py are bitwise only for the launches on stored value runs), so the
+        replay test cannot be run for it.  Take kkt(...) outside the capture; everything on the returned PoseKKTValues is replayable."""
         torch = _torch()
         self._check("x", x, (self.batch, self.n))
+        _refuse("PoseNLP.kkt", _NO_REFERENCE, "Take kkt(...) outside the capture and capture what runs on it: matvec, diagonal_preconditioner, solve, factor, solve_direct")
         sigma = self._sigma(sigma)
         self._check("lam", lam, (self.batch, self.m))
         jac = torch.empty(self.batch, self.engine.nnz, dtype=torch.float64, device=self.device)

@@ -450,7 +450,7 @@ int hipnlp_eval_hess_vec_device(hipnlp_handle* h, const double* x_dev, const dou
 /* out = H v from a value run values_dev [batch][nnz_h] that hipnlp_eval_hess_device of the SAME handle wrote: for many products at one x
  * (the inner iterations of a CG solve).  No x, no parameters, no multipliers; v_dev, out_dev [batch][n], out_dev may not alias v_dev;
  * stream rules and error codes as above (no HIPNLP_E_PARAMS).  Order and arithmetic are those of hipnlp_eval_hess_vec_device: bit for
- * bit its result. */
+ * bit its result.  Replayable from a captured graph after one eager call on the handle (tests/test_gpu_graph_replay.py). */
 int hipnlp_hess_times_device(hipnlp_handle* h, const double* values_dev, const double* v_dev, double* out_dev, void* stream);
 
 /* Products with a STORED value run of jac g, for many products at one x (the inner iterations of a Krylov solve on the KKT system): no
@@ -472,7 +472,9 @@ int hipnlp_hess_times_device(hipnlp_handle* h, const double* values_dev, const d
  * hipnlp_eval_lagrangian_grad_device, obj_factor grad f_c first (+0.0 without a gradient).
  *
  * Return HIPNLP_E_INVALID for a missing required pointer, HIPNLP_E_UNSUPPORTED on a multi-device handle, on a shard handle (knot_begin /
- * knot_end not the whole horizon) and for a layout whose tables exceed what the kernels stage (hipnlp_last_error says which). */
+ * knot_end not the whole horizon) and for a layout whose tables exceed what the kernels stage (hipnlp_last_error says which).
+ * Both: replayable from a captured graph after one eager call on the handle — for hipnlp_jac_times_device an eager call WITH dot_dev where the captured one
+ * has it: the dot's partials are allocated the first time a dot is asked for (tests/test_gpu_graph_replay.py). */
 int hipnlp_jac_times_device(hipnlp_handle* h, const double* jac_values_dev, const double* grad_values_dev, const double* v_dev,
                             double* jv_dev, double* dot_dev, void* stream);
 int hipnlp_jac_transpose_times_device(hipnlp_handle* h, const double* jac_values_dev, const double* grad_values_dev,
@@ -502,7 +504,7 @@ int hipnlp_jac_transpose_times_device(hipnlp_handle* h, const double* jac_values
  *
  * Returns HIPNLP_E_INVALID for a missing handle or required pointer (all but dx_dev and dc_dev), HIPNLP_E_UNSUPPORTED on a multi-device
  * handle, on a shard handle (knot_begin / knot_end not the whole horizon) and for a layout whose tables exceed what the kernel stages
- * (hipnlp_last_error says which).  No HIPNLP_E_PARAMS. */
+ * (hipnlp_last_error says which).  No HIPNLP_E_PARAMS.  Replayable from a captured graph after one eager call on the handle (tests/test_gpu_graph_replay.py). */
 int hipnlp_kkt_times_device(hipnlp_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev,
                             const double* dc_dev, const double* v_dev, const double* w_dev, double* top_dev, double* bottom_dev,
                             void* stream);
@@ -548,7 +550,9 @@ int hipnlp_kkt_times_device(hipnlp_handle* h, const double* hess_values_dev, con
  *
  * Returns as hipnlp_kkt_times_device (HIPNLP_E_INVALID for a missing handle or required pointer — all but dx_dev, dc_dev and the two
  * minv; HIPNLP_E_UNSUPPORTED on a multi-device handle, a shard handle, a layout beyond the caps), and HIPNLP_E_INVALID for rtol < 0,
- * max_iterations < 0, check_every < 0 and for exactly one of the two minv pointers. */
+ * max_iterations < 0, check_every < 0 and for exactly one of the two minv pointers.
+ * With check_every = 0: replayable from a captured graph after one eager call on the handle; every replay starts from zero, whatever
+ * status the previous replay or a solve in between left in the workspace (tests/test_gpu_graph_replay.py). */
 int hipnlp_kkt_minres_device(hipnlp_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev,
                              const double* dc_dev, const double* minv_top_dev, const double* minv_bottom_dev, const double* rhs_top_dev,
                              const double* rhs_bottom_dev, double* sol_top_dev, double* sol_bottom_dev, double rtol, int max_iterations,
@@ -584,7 +588,7 @@ int hipnlp_kkt_minres_reserve(hipnlp_handle* h, int64_t* bytes_out);
  *
  * Returns as hipnlp_kkt_times_device (HIPNLP_E_INVALID for a missing handle or required pointer — all but dx_dev and dc_dev;
  * HIPNLP_E_UNSUPPORTED on a multi-device handle, a shard handle, a layout beyond the caps), and HIPNLP_E_INVALID for a floor that is not
- * a finite number > 0. */
+ * a finite number > 0.  Replayable from a captured graph after one eager call on the handle (tests/test_gpu_graph_replay.py). */
 int hipnlp_kkt_diag_precond_device(hipnlp_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev,
                                    const double* dc_dev, double floor, double* minv_top_dev, double* minv_bottom_dev, void* stream);
 
@@ -618,7 +622,9 @@ int hipnlp_kkt_diag_precond_device(hipnlp_handle* h, const double* hess_values_d
  * null handle or required pointer (all but dx_dev / dc_dev), a floor that is not a finite number > 0, rtol < 0, max_iterations < 0,
  * check_every < 0 — refused before anything is launched.  HIPNLP_E_UNSUPPORTED as hipnlp_kkt_diag_precond_device.  Measured:
  * profiles/r16_kkt_block.txt (tools/kkt_block_probe.py).  NOT claimed: that an interior-point step is cheap with it; systems with
- * diagonals a factor 1e-4 smaller than U[1, 2] were not seen to converge with either preconditioner. */
+ * diagonals a factor 1e-4 smaller than U[1, 2] were not seen to converge with either preconditioner.
+ * The factor, the apply and (with check_every = 0) the solve: replayable from a captured graph after one eager call on the handle
+ * (tests/test_gpu_graph_replay.py). */
 int hipnlp_kkt_block_bytes(const hipnlp_handle* h, int64_t* bytes_out /*[4]*/);
 int hipnlp_kkt_block_factor_device(hipnlp_handle* h, const double* hess_values_dev, const double* dx_dev /*or NULL*/, double floor, double* factor_dev,
                                    int32_t* pivots_dev, double* e_dev, double* o_dev, int32_t* inertia_dev, int32_t* status_dev, void* stream);
@@ -656,7 +662,7 @@ int hipnlp_kkt_minres_block_device(hipnlp_handle* h, const double* hess_values_d
  * factorisations for the slowest knot of a launch; measured: profiles/r17_kkt_ladder.txt (tools/kkt_ladder_probe.py).
  * HIPNLP_E_INVALID, refused before anything is launched: what hipnlp_kkt_block_factor_device refuses, a null delta_dev or tries_dev,
  * max_tries outside 0 .. 16, and with max_tries > 0 a delta_init that is not a finite number > 0 or a kappa that is not a finite number
- * > 1.  HIPNLP_E_UNSUPPORTED as hipnlp_kkt_block_factor_device. */
+ * > 1.  HIPNLP_E_UNSUPPORTED as hipnlp_kkt_block_factor_device.  Replayable from a captured graph after one eager call on the handle (tests/test_gpu_graph_replay.py). */
 int hipnlp_kkt_block_ladder_device(hipnlp_handle* h, const double* hess_values_dev, const double* dx_dev /*or NULL*/, double floor, double delta_init, double kappa,
                                    int max_tries, double* factor_dev, int32_t* pivots_dev, double* e_dev, double* o_dev, int32_t* inertia_dev, int32_t* status_dev,
                                    double* delta_dev /*[batch][N]*/, int32_t* tries_dev /*[batch][N]*/, void* stream);
@@ -682,7 +688,7 @@ int hipnlp_kkt_block_ladder_device(hipnlp_handle* h, const double* hess_values_d
  * a null minv_top_dev or minv_bottom_dev.  HIPNLP_E_UNSUPPORTED as hipnlp_kkt_block_factor_device (multi-device and shard handles
  * included), and a layout whose column block has more than 1 620 entries or is touched by more than 439 rows.
  * Measured: 1.14 x hipnlp_kkt_block_factor_device's launch at 100 x 1, 100 x 64 and stairs 200 x 16 (profiles/r18_kkt_condensed.txt,
- * tools/kkt_condensed_probe.py). */
+ * tools/kkt_condensed_probe.py).  Replayable from a captured graph after one eager call on the handle (tests/test_gpu_graph_replay.py). */
 int hipnlp_kkt_condensed_factor_device(hipnlp_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev /*or NULL*/,
                                        const double* dc_dev /*required*/, double floor, double* factor_dev, int32_t* pivots_dev, double* e_dev, double* o_dev,
                                        int32_t* inertia_dev, int32_t* status_dev, double* minv_top_dev /*[batch][n]*/, double* minv_bottom_dev /*[batch][m]*/, void* stream);
@@ -999,7 +1005,8 @@ int hipnlp_pose_eval_hess_vec_device(hipnlp_pose_handle* h, const double* x_dev,
  * HIPNLP_E_INVALID: a null handle or required pointer, floor not a finite number > 0, rtol < 0 or NaN, max_iterations < 0 or above
  * 4096 (what one launch may run on a shared device), one of minv_top_dev / minv_bottom_dev alone, or either with build_diagonal.
  * HIPNLP_E_UNSUPPORTED: the handle's pattern is beyond what a workgroup stages (1024 entries of jac g, 256 rows, 768 entries and 1536
- * touches of the Hessian); nothing is truncated.  Measured: hippopt_amd/autograd.py PoseKKTValues.solve and profiles/r14_pose_kkt.txt. */
+ * touches of the Hessian); nothing is truncated.  Measured: hippopt_amd/autograd.py PoseKKTValues.solve and profiles/r14_pose_kkt.txt.
+ * All three: replayable from a captured graph after one eager call on the handle (tests/test_gpu_graph_replay.py). */
 int hipnlp_pose_kkt_times_device(hipnlp_pose_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* v_dev /*[batch][81]*/,
                                  const double* w_dev /*[batch][m]*/, double* top_dev /*[batch][81]*/, double* bottom_dev /*[batch][m]*/,
                                  const double* dx_dev /*or NULL*/, const double* dc_dev /*or NULL*/, void* stream);
@@ -1040,7 +1047,8 @@ int hipnlp_pose_kkt_minres_device(hipnlp_pose_handle* h, const double* hess_valu
  * HIPNLP_E_INVALID: a null handle or required pointer, nrhs out of range, one of factor_dev / pivots_dev alone, max_tries outside
  * 0 .. 16, and with max_tries > 0 a delta_init that is not a finite number > 0 or a kappa that is not a finite number > 1.
  * HIPNLP_E_UNSUPPORTED: the handle's pattern is beyond hipnlp_pose_kkt_times_device's caps or 81 + m > 176.  Measured:
- * profiles/r15_pose_ldl.txt (tools/pose_ldl_probe.py) — 0.24 x torch.linalg.solve on the dense K, slower than MINRES at dx, dc in U[1, 2]. */
+ * profiles/r15_pose_ldl.txt (tools/pose_ldl_probe.py) — 0.24 x torch.linalg.solve on the dense K, slower than MINRES at dx, dc in U[1, 2].
+ * Both launches: replayable from a captured graph after one eager call on the handle (tests/test_gpu_graph_replay.py). */
 int hipnlp_pose_kkt_ldl_doubles(const hipnlp_pose_handle* h);
 int hipnlp_pose_kkt_ldl_device(hipnlp_pose_handle* h, const double* hess_values_dev, const double* jac_values_dev, const double* dx_dev /*or NULL*/,
                                const double* dc_dev /*or NULL*/, int nrhs, const double* rhs_top_dev, const double* rhs_bottom_dev, double* sol_top_dev,

@@ -1,6 +1,13 @@
 #!/usr/bin/env python3
 """GPU box: are K back-to-back callback launches cheaper as ONE hipGraph launch?  Captures K hipnlp_eval_device calls (torch's stream
-capture around the library's launches) and times replays against the same K launches issued on the stream."""
+capture around the library's launches) and times replays against the same K launches issued on the stream.
+
+A TIMING probe only.  Its "outputs_of_the_last_step_equal" proves nothing about correctness under replay: every replay runs the same
+four x, so a replay that returned the previous replay's f would return the right number.  That is what hipnlp_eval_device can do: the
+cost reducer accepts a knot's partial by the launch number, a captured launch bakes that number in, and on the second replay every
+partial of the first still carries it (include/hipnlp.h: "not replayable from a captured hipGraph").  So these launches are NOT
+capturable as they are; the torch layer refuses nlp(x) while a stream is capturing, and what does replay is listed in DESIGN.md, "Graph
+capture" (tests/test_gpu_graph_replay.py)."""
 import json
 import os
 import sys
